@@ -27,7 +27,11 @@ cpu_baseline: the CPU oracle (oracle/, a C port of the reference algorithm + the
            RCCL all_gather of the packed results per step).  With --gpus N > 1 the default run adds a short sharded
            S300 leg as a secondary field.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 via torch.distributed.run.
+Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 via torch.distributed.run.  A plain run sets up, warms
+           up, times ONE region of exactly K steps and prints the headline line (value, ms_per_step, config, host).  --full
+           adds everything else above (three timed regions, the median reported; single_batch, per-kernel times, rooflines,
+           cpu_baseline, one_pass / stream / end_to_end, shape, pools_long, alignment, strong-scaling proxy; N > 1: the
+           sharded legs).  --dump-outputs DIR writes the results of the last timed step as .npy arrays (dump_outputs).
 """
 import argparse
 import hashlib
@@ -303,6 +307,67 @@ def mean_fs(results):
     fs_c = [r[2][3] for r in results]
     fs_b = [r[3][3] for r in results]
     return sum(fs_c) / len(fs_c), sum(fs_b) / len(fs_b)
+
+
+DUMP_SAMPLE, DUMP_SEED, DUMP_CAP = 2048, 150, 64 << 20
+
+
+def dump_outputs(batches, nset, npsets, outdir):
+    """--dump-outputs DIR: what the timed path handed its caller after its last step -- per record the SQRNdbnseq tuple
+    (consensus, [(dot-bracket, scores, paramsets)], consensus metrics, best-of-top metrics) and the reference scores
+    (Batch.result(k, with_ref=True)) -- as .npy arrays.  Records: the first set of the first batch in full, then a fixed
+    sample (seed DUMP_SEED) of DUMP_SAMPLE other records in flight; the whole SRtest150 x 8 x 12 would be ~110 MB.  Dot-bracket
+    lines are their code points (float32, exact), concatenated, with float64 offsets; metrics are NaN where a record has no
+    reference structure.  Records are dropped from the end of the sample only if the files would exceed 64 MB."""
+    import numpy as np
+    per = batches[0].nseq
+    total = len(batches) * per
+    rng = np.random.default_rng(DUMP_SEED)
+    rest = np.arange(nset, total)
+    pick = list(range(min(nset, total))) + sorted(rng.choice(rest, min(DUMP_SAMPLE, len(rest)), replace=False).tolist())
+    rows, cons, dbn, cons_off, dbn_off, counts, scores, member, met_c, met_b, refsc = [], [], [], [0], [0], [], [], [], [], [], []
+    nbytes = 0
+    for g in pick:
+        b, k = divmod(g, per)
+        (c, preds, mc, mb), ref = batches[b].result(k, with_ref=True)
+        size = 4 * len(c) * (1 + len(preds)) + 8 * 3 + len(preds) * (8 + 24 + 4 * npsets) + 8 * 19
+        if nbytes + size > DUMP_CAP - (1 << 20):
+            break
+        nbytes += size
+        rows.append((b, k // nset, k % nset))
+        cons.append(c)
+        cons_off.append(cons_off[-1] + len(c))
+        counts.append(len(preds))
+        for s, sc, ps in preds:
+            dbn.append(s)
+            dbn_off.append(dbn_off[-1] + len(s))
+            scores.append(sc)
+            m = [0.0] * npsets
+            for q in ps:
+                m[q] = 1.0
+            member.append(m)
+        met_c.append(mc)
+        met_b.append(mb)
+        refsc.append(ref if ref is not None else (np.nan,) * 3)
+
+    def codes(lines):
+        return np.frombuffer("".join(lines).encode("utf-32-le"), "<u4").astype(np.float32)
+
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {
+        "record_index": np.array(rows, np.float64).reshape(-1, 3),       # (batch, set copy, record of SRtest150)
+        "consensus_dbn": codes(cons), "consensus_offsets": np.array(cons_off, np.float64),
+        "structure_count": np.array(counts, np.float64),
+        "structure_dbn": codes(dbn), "structure_offsets": np.array(dbn_off, np.float64),
+        "structure_scores": np.array(scores, np.float64).reshape(-1, 3),
+        "structure_paramsets": np.array(member, np.float32).reshape(-1, npsets),
+        "metrics_consensus": np.array(met_c, np.float64).reshape(-1, 6),
+        "metrics_best": np.array(met_b, np.float64).reshape(-1, 7),
+        "reference_scores": np.array(refsc, np.float64).reshape(-1, 3),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return dict(dir=outdir, records=len(rows), structures=len(dbn), bytes=int(sum(a.nbytes for a in arrays.values())))
 
 
 # ---------------------------------------------------------------- PMC summaries (profiles/traffic.json)
@@ -1062,13 +1127,22 @@ def main():
     ap.add_argument("--workload", default="srtest150", choices=["srtest150", "S300", "S1000", "S2000"])
     ap.add_argument("--sub-batches", type=int, default=0,
                     help="strong-scaling mode: concurrent batches per rank (0 = the workload's measured best: %s)" % SUB_BATCHES)
-    ap.add_argument("--regions", type=int, default=3, help="timed regions of `steps` steps each; the median one is reported")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-stream", action="store_true", help="skip the stream / one_pass legs")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the S1000 roofline leg")
-    ap.add_argument("--no-alignment", action="store_true", help="skip the alignment leg (BASELINE config 5)")
+    ap.add_argument("--regions", type=int, default=0,
+                    help="timed regions of `steps` steps each; the median one is reported (0 = 1, with --full 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every secondary leg (single batch, per-kernel times, rooflines, CPU baselines, one_pass / stream / "
+                         "end_to_end, shape, pools_long, alignment, strong-scaling proxy; with N > 1 the sharded legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as .npy arrays into DIR (see dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-stream", action="store_true", help="--full: skip the stream / one_pass legs")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the S1000 roofline leg")
+    ap.add_argument("--no-alignment", action="store_true", help="--full: skip the alignment leg (BASELINE config 5)")
     ap.add_argument("--roofline-seqs", type=int, default=1024)    # S1000 = 1,024 sequences
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "srtest150":
+        ap.error("--dump-outputs writes the SRtest150 headline's results; it does not apply to --workload %s" % args.workload)
+    regions = args.regions if args.regions > 0 else (3 if args.full else 1)
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1077,7 +1151,7 @@ def main():
 
     recs = load_srtest150()
     cpu = cpu_workers = None
-    if rank == 0 and world == 1 and not args.no_cpu and args.workload == "srtest150":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and args.workload == "srtest150":
         cpu_workers = cpu_workers_start(recs, args.config)   # before any GPU initialisation; the leg itself runs last
 
     import torch
@@ -1136,10 +1210,11 @@ def main():
         torch.cuda.synchronize()
 
     run(args.warmup)
-    # Three timed regions of exactly `steps` steps each, every one bracketed by barrier + synchronize and reduced with MAX
-    # over the ranks; the line reports the MEDIAN region (the folds are chains of short kernels: host jitter shows).
-    regions = []
-    for _ in range(max(1, args.regions)):
+    # Timed regions of exactly `steps` steps each (one; three with --full), every one bracketed by barrier + synchronize and
+    # reduced with MAX over the ranks; the line reports the MEDIAN region (the folds are chains of short kernels: host
+    # jitter shows).
+    regions_t = []
+    for _ in range(regions):
         fence()
         t0 = time.perf_counter()
         cpu0 = time.process_time()
@@ -1151,14 +1226,54 @@ def main():
             t = torch.tensor([dt], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        regions.append((dt, host_cpu))
-    region_ms = [round(r[0] / args.steps * 1e3, 3) for r in regions]
-    dt, host_cpu = sorted(regions)[len(regions) // 2]
+        regions_t.append((dt, host_cpu))
+    region_ms = [round(r[0] / args.steps * 1e3, 3) for r in regions_t]
+    dt, host_cpu = sorted(regions_t)[len(regions_t) // 2]
 
-    # ---- secondary, OUTSIDE the timed region ----------------------------------------------------------------------
+    evals = sum(batches[0].evals(k) for k in range(nset))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batches, nset, len(names), args.dump_outputs)
+    per_step = nset * R * K
+    head = {
+        "metric": "sequences/sec (SRtest150, single-sequence mode)",
+        "value": round(per_step * world * args.steps / dt, 1),
+        "unit": "seq/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "timed_regions_ms_per_step": region_ms,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "dtype_note": "scores and every decision in fp64, in the reference's operation order; the scan itself works on 1-bit cell activity",
+        "data": "SRtest150.fas shipped with the reference (219 records, 8-150 nt, reference dbn per record)",
+        "config": {"workload": "SRtest150 if=qf c=%s poollim=1000; %d independent batches in flight per GPU (sq_fold_concurrent, "
+                               "one stream set each), each holding the 219-record set %d time(s); a step folds all of them; the "
+                               "batches run free inside the timed region (every batch is folded `steps` times back to back, "
+                               "no barrier between the steps: sq_fold_concurrent_n)" % (args.config, K, R),
+                   "batches_in_flight": K, "sets_per_batch": R, "host_cpus": effective_cpus(),
+                   "host_threads_per_batch": host_threads(K, local_world), "seqs_per_gpu_per_step": per_step,
+                   "paramsets": names, "evals_R_per_step": int(evals) * K * R, "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")},
+        "host": {"cpu_ms_per_step": round(host_cpu / args.steps * 1e3, 1), "busy_cpus": round(host_cpu / dt, 1),
+                 "cpu_quota": effective_cpus(),
+                 "note": "rank 0's process CPU time inside the timed region (all threads): launches and waits of the fold threads; "
+                         "RunAlgo's filters, the edge lists and the ranking tails run on the device"},
+    }
+    if not args.full:                                         # the headline alone: set-up, warm-up, the timed steps, the line
+        for b in batches:
+            b.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(head))
+        return
+
+    # ---- --full: secondary, OUTSIDE the timed region --------------------------------------------------------------
     results = [batches[0].result(k) for k in range(nset)]
     fs_c, fs_b = mean_fs(results)
-    evals = sum(batches[0].evals(k) for k in range(nset))
     same = all(repr(b.result(k + r * nset)) == repr(results[k]) for b in batches for r in range(R) for k in range(r, nset, 7))
     for b in batches:
         b.close()
@@ -1352,37 +1467,11 @@ def main():
             pass
     if rank != 0:
         return
-    per_step = nset * R * K
-    line = {
-        "metric": "sequences/sec (SRtest150, single-sequence mode)",
-        "value": round(per_step * world * args.steps / dt, 1),
-        "unit": "seq/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "timed_regions_ms_per_step": region_ms,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "dtype_note": "scores and every decision in fp64, in the reference's operation order; the scan itself works on 1-bit cell activity",
-        "data": "SRtest150.fas shipped with the reference (219 records, 8-150 nt, reference dbn per record)",
-        "config": {"workload": "SRtest150 if=qf c=%s poollim=1000; %d independent batches in flight per GPU (sq_fold_concurrent, "
-                               "one stream set each), each holding the 219-record set %d time(s); a step folds all of them; the "
-                               "batches run free inside the timed region (every batch is folded `steps` times back to back, "
-                               "no barrier between the steps: sq_fold_concurrent_n)" % (args.config, K, R),
-                   "batches_in_flight": K, "sets_per_batch": R, "host_cpus": effective_cpus(),
-                   "host_threads_per_batch": host_threads(K, local_world), "seqs_per_gpu_per_step": per_step,
-                   "paramsets": names, "evals_R_per_step": int(evals) * K * R, "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")},
+    line = dict(head, **{
         "single_batch": {"ms_per_fold": round(lat[len(lat) // 2], 3), "best_ms": round(lat[0], 3),
                          "seq_per_s": round(len(prepared) / lat[len(lat) // 2] * 1e3, 1),
                          "how": "ONE 219-record batch alone (a fresh batch, nothing else in flight), median / best of 10 folds"},
         "single_batch_greedynobpp": greedy_alone,
-        "host": {"cpu_ms_per_step": round(host_cpu / args.steps * 1e3, 1), "busy_cpus": round(host_cpu / dt, 1),
-                 "cpu_quota": effective_cpus(),
-                 "note": "rank 0's process CPU time inside the timed region (all threads): launches and waits of the fold threads; "
-                         "RunAlgo's filters, the edge lists and the ranking tails run on the device"},
         "kernel_ms_per_fold": kernel_ms,
         "f1": {"mean_FS_consensus": round(fs_c, 4), "mean_FS_best_of_top5": round(fs_b, 4),
                "batches_in_flight_agree": bool(same)},
@@ -1408,7 +1497,7 @@ def main():
         "strong_scaling_proxy": proxy,
         "sharded": sharded,
         "n_ranks_seen": world if world == 1 else nranks_seen,
-    }
+    })
     print(json.dumps(line))
 
 

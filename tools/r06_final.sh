@@ -15,7 +15,7 @@ pa 3 FETCH_SIZE
 pa 4 WRITE_SIZE TCC_HIT_sum TCC_MISS_sum
 { for k in sq_rounds_kernel sq_scatter_all_kernel sq_colselect_kernel; do echo "== $k"; python3 tools/pmc_summary.py $a $k; done; } > profiles/${tag}_a5000_pmc.txt
 # the headline step under the counters, kernel by kernel (separate passes)
-pb="bench.py --steps 2 --warmup 1 --regions 1 --no-cpu --no-stream --no-roofline --no-alignment"
+pb="bench.py --full --steps 2 --warmup 1 --regions 1 --no-cpu --no-stream --no-roofline --no-alignment"
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $o/pmc_bench/p1 -- python3 $pb > $o/pmc_bench1.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS --output-format csv -d $o/pmc_bench/p2 -- python3 $pb > $o/pmc_bench2.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $o/pmc_bench/p3 -- python3 $pb > $o/pmc_bench3.log 2>&1
@@ -27,8 +27,8 @@ python3 tools/pmc_summary.py gpurun_out/pmc_r06_pl sq_pool_round_root_kernel > p
 python3 tools/make_traffic.py $tag sq_pool_round_root_kernel=gpurun_out/pmc_r06_pl sq_rounds_kernel=gpurun_out/pmc_${tag}_s1000 sq_mwm_kernel:sq_mwm=gpurun_out/pmc_${tag}_mwm sq_fill_kernel=gpurun_out/pmc_${tag}_fill sq_pool_round_kernel=$o/pmc_bench \
     a5000_rounds:sq_rounds_kernel=$a a5000_scatter:sq_scatter_all_kernel=$a a5000_colselect:sq_colselect_kernel=$a > /dev/null
 cp profiles/${tag}_*_pmc.txt profiles/traffic.json $o/
-python bench.py --steps 20 --warmup 3 > $o/bench.out 2> $o/bench.err; tail -1 $o/bench.out > $o/${tag}_bench.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats -- python3 bench.py --steps 20 --warmup 3 --no-cpu > $o/stats.log 2>&1
+python bench.py --full --steps 20 --warmup 3 > $o/bench.out 2> $o/bench.err; tail -1 $o/bench.out > $o/${tag}_bench.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu > $o/stats.log 2>&1
 cp $(ls $o/stats/*/*kernel_stats.csv | head -1) $o/${tag}_bench_kernel_stats.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/s1000 -- python3 tools/s1000_probe.py 1024 1000 5 --noprof > $o/s1000.log 2>&1
 cp $(ls $o/s1000/*/*kernel_stats.csv | head -1) $o/${tag}_s1000_kernel_stats.csv

@@ -157,7 +157,7 @@ struct JobBuild { int n = 0; size_t ncell = 0, need = 0, nout = 0; };
 // Hungarian kernel: 1.0 + 1.5 ms then ended after the critical class did)
 static inline int side_of(const sq_batch *b, int slot)
 {
-    static const int forced = getenv("SQ_SIDE_STREAMS") ? atoi(getenv("SQ_SIDE_STREAMS")) : 0;
+    const int forced = sq_tuning().side_streams;
     const int nside = forced ? forced : b->side_streams;
     if (slot == 3) return nside >= 3 ? 3 : (nside == 2 ? 1 : 0);
     return nside >= 3 ? slot : (nside == 2 ? (slot == 0 ? 0 : 1) : 0);
@@ -288,7 +288,7 @@ static int algo_build(sq_batch *b, const std::vector<int> &jobs, const std::vect
         // Two classes for Edmonds, one for Hungarian: classes that FOLLOW each other on a stream each last as long as
         // their slowest job, so more of them lengthen the chain on the short kernels' stream past the end of Edmonds'
         // class 0 (traced: 4 + 4 classes end at 9.3 ms, one batch alone, instead of 7.2 ms)
-        static const int env_classes = getenv("SQ_MWM_CLASSES") ? std::max(1, atoi(getenv("SQ_MWM_CLASSES"))) : 0;
+        const int env_classes = sq_tuning().mwm_classes;
         // (Edmonds: one launch, the graphs packed into multi-wave blocks by LDS need -- sq_mwm_plan)
         // and with one batch alone in two size classes of one-graph blocks, the critical class on its own stream)
         // Hungarian with the chip crowded (batches in flight, or thousands of jobs): every block of a launch gets the LDS of the
@@ -390,7 +390,7 @@ static int algo_launch(sq_batch *b, SqAlgoChunk &ck, char *region, hipStream_t s
             const int rl = sq_launch_matching(algo, ck.sorted.data() + c.start, c.count, d_jobs + c.start, d_edges, ck.nedges,
                                               (SqMatchEdge *)(region + o_edges), d_scr, ck.d_out, ck.d_cnt, b->ctx.codes,
                                               ck.job_flags ? ck.job_flags + c.start : nullptr, ck.flag_val, cs,
-                                              ck.p_jobs + c.start, ck.bin_head ? ck.bin_head + c.start : nullptr, b->inflight);
+                                              ck.p_jobs + c.start, ck.bin_head ? ck.bin_head + c.start : nullptr, b->inflight, b->sw.mwm_dump);
             if (rl) return sq_check((hipError_t)rl, "matching kernel launch");
         }
         if (other && ck.classes.size() > 1) {
@@ -468,14 +468,12 @@ static int algo_collect(sq_batch *b, const std::vector<int> &jobs, const std::ve
                 b->mwm_stats[0]++; b->mwm_stats[1] += np;
                 if (np > b->mwm_stats[2]) { b->mwm_stats[2] = np; b->mwm_stats[3] = ne; b->mwm_stats[4] = mj[q].n; b->mwm_stats[5] = mj[q].nedges; }
             }
-            static const bool posthoc = getenv("SQ_MWM_POSTHOC") != nullptr;
-            if (posthoc) {                                     // debug: what this read saw, to be compared after the fold
+            if (b->sw.mwm_posthoc) {                           // debug: what this read saw, to be compared after the fold
                 uint64_t h = 1469598103934665603ull;
                 for (int v = 0; v < 2 * mj[q].n + 2; v++) { h ^= (uint32_t)mate[v]; h *= 1099511628211ull; }
                 if (ck.seen_hash.size() == mj.size()) ck.seen_hash[q] = h;
             }
-            static const bool verify = getenv("SQ_MWM_VERIFY") != nullptr;
-            if (verify && mj[q].n > 0) {
+            if (sq_tuning().mwm_verify && mj[q].n > 0) {
                 // debug: the same algorithm object run on the host over the job's edges must give the kernel's mates
                 const SqMatchEdge *he = ck.p_edges + mj[q].edge_off;
                 std::vector<char> scr(SqBlossom::scratch_bytes(mj[q].n, mj[q].nedges) + 64);
@@ -662,8 +660,7 @@ static int algos_begin_dev(sq_batch *b, SqAlgoAsync *pa, int levellimit_opt)
             need_raw.push_back(nr);
         }
     }
-    static const bool no_raw = getenv("SQ_NO_ALGO_RAW") != nullptr;      // (measurement: such batches take the host-driven form)
-    if (raw_cap && no_raw) return 1;
+    if (raw_cap && sq_tuning().no_algo_raw) return 1;      // (measurement: such batches take the host-driven form)
     if (maxn > SQ_ALGO_MAXN || maxn < 1) return 1;
     tmax = std::max(b->chain_tmax, 1);
     const size_t fin_lds = sq_algo_finish_lds(maxn, tmax);
@@ -792,7 +789,7 @@ static int algos_begin_dev(sq_batch *b, SqAlgoAsync *pa, int levellimit_opt)
         const SqAlgoJob *edges_aj = round_aj;
         {
             const size_t at = (b->algo_used + 255) & ~(size_t)255, need = (size_t)S * sizeof(SqAlgoJob);
-            if (b->algo_scratch && at + need <= b->algo_bytes && !getenv("SQ_NO_STATE_COPY")) {
+            if (b->algo_scratch && at + need <= b->algo_bytes && !sq_tuning().no_state_copy) {
                 HIPCK(hipMemcpyAsync(b->algo_scratch + at, round_aj, need, hipMemcpyHostToDevice, st));
                 edges_aj = (const SqAlgoJob *)(b->algo_scratch + at);
             }
@@ -847,7 +844,7 @@ static int algos_begin_dev(sq_batch *b, SqAlgoAsync *pa, int levellimit_opt)
                 rl = sq_launch_matching(it.algo, ck.sorted.data() + c2.start, c2.count, ck.p_jobs + c2.start, d_edges, ck.nedges,
                                         const_cast<SqMatchEdge *>(d_edges), region + cv[q].o_scr, d_out, d_cnt, b->ctx.codes, nullptr, ck.flag_val,
                                         (cidx > 0 && other) ? other : cs,
-                                        ck.p_jobs + c2.start, ck.bin_head ? ck.bin_head + c2.start : nullptr, b->inflight);
+                                        ck.p_jobs + c2.start, ck.bin_head ? ck.bin_head + c2.start : nullptr, b->inflight, b->sw.mwm_dump);
             }
             if (other && !rl) { HIPCK(hipEventRecord(b->class_ev, other)); HIPCK(hipStreamWaitEvent(cs, b->class_ev, 0)); }
         }

@@ -8,10 +8,10 @@
 // diagonal bit matrix of a job (sq_bits_kernel): nw word-rows of bpitch words
 static inline int32_t bits_nw(int n) { return (n + 31) / 32; }
 static inline int32_t bits_pitch(int n) { return (int32_t)align_up((size_t)2 * n, 64) + 64; }
-static inline int32_t ld_of(int n)
+static inline int32_t ld_of(int n, const SqBatchSwitches &sw)
 {
     int k = (std::max(n, 1) - 1 + 31) / 32;
-    if (!getenv("SQ_LD_POW2") && (k & 1) == 0) k++;
+    if (!sw.ld_pow2 && (k & 1) == 0) k++;
     return 32 * k + 1;
 }
 
@@ -61,6 +61,7 @@ static int64_t pow17_entries(const sq_paramset &ps, int maxn, double &scale)
 
 namespace {
 struct Layout {
+    SqBatchSwitches sw;              // (sq_switches.h: read by plan)
     size_t off_codes, off_flags, off_inc4, off_chain, off_e0, off_reacts, off_ridx, off_jobs, off_psets, off_sdf, off_rftab, off_powtab;
     int64_t n_rftab, pow_entries;
     size_t off_mat32, off_mat64, off_structs, off_strands, off_state, off_cnt, off_ctr, off_cands, off_out;
@@ -90,6 +91,7 @@ struct Layout {
 int plan(const sq_batch_desc *d, Layout &L)
 {
     if (!d || d->nseq <= 0 || d->njobs <= 0 || d->npset <= 0) { sq_set_error("empty batch"); return -1; }
+    sq_read_batch_switches(L.sw);
     L.ltot = d->seq_off[d->nseq];
     L.maxn = 0;
     for (int s = 0; s < d->nseq; s++) L.maxn = std::max(L.maxn, d->seq_off[s + 1] - d->seq_off[s]);
@@ -97,7 +99,7 @@ int plan(const sq_batch_desc *d, Layout &L)
     L.max_structs = d->max_structs > 0 ? d->max_structs : 4096;
     L.cpn = d->cand_per_nt > 0 ? d->cand_per_nt : 32;
     L.mat32_floats = 0; L.mat64_doubles = 0; L.bits_words = 0;
-    L.mul_direct = d->mul_matrix_dev != nullptr && getenv("SQ_MUL_GATHER") == nullptr;
+    L.mul_direct = d->mul_matrix_dev != nullptr && !L.sw.mul_gather;
     int64_t sum_cap = 0;
     for (int j = 0; j < d->njobs; j++) {
         const int s = d->job_seq[j];
@@ -107,7 +109,7 @@ int plan(const sq_batch_desc *d, Layout &L)
                              (d->bpp_term && d->bpp_term[j]) || (d->mul_shared && d->mul_shared[j]);
         // (jobs weighted by the shared stem matrix need no fp32 matrix: their product is formed by the gather kernel)
         const bool shared_only = d->mul_shared && d->mul_shared[j] && !(d->ext_score && d->ext_score[j]);
-        if (want_fp32(d) || (ext_any && !shared_only)) L.mat32_floats += (int64_t)align_up((size_t)(n * ld_of((int)n)), 64);
+        if (want_fp32(d) || (ext_any && !shared_only)) L.mat32_floats += (int64_t)align_up((size_t)(n * ld_of((int)n, L.sw)), 64);
         L.bits_words += (int64_t)bits_nw((int)n) * bits_pitch((int)n);
         const bool ext = d->ext_score && d->ext_score[j];
         const bool mul = (d->mul_score && d->mul_score[j]) || (d->bpp_term && d->bpp_term[j]) ||
@@ -115,7 +117,7 @@ int plan(const sq_batch_desc *d, Layout &L)
         if (ext) L.mat64_doubles += 2 * n * n;
         else if (mul) L.mat64_doubles += n * n;
     }
-    L.mat32_floats += 1024 + (int64_t)160 * ld_of(L.maxn);     // reads of rows past a short segment stay inside the arena
+    L.mat32_floats += 1024 + (int64_t)160 * ld_of(L.maxn, L.sw);     // reads of rows past a short segment stay inside the arena
     L.sdf_len = 0;
     for (int p = 0; p < d->npset; p++) {
         const double bw = d->psets[p].bracketweight;
@@ -144,7 +146,7 @@ int plan(const sq_batch_desc *d, Layout &L)
     // the dense fp64 read-back (sq_bpmatrix_read) borrows the candidate arena
     L.cand_records = std::max<int64_t>(L.cand_records, (int64_t)(2 * (int64_t)L.maxn * L.maxn * 8 / sizeof(SqCand)) + 16);
     L.out_cap = (uint32_t)std::min<int64_t>(L.cand_records, (int64_t)4 << 20);
-    if (const char *e = getenv("SQ_OUT_CAP")) L.out_cap = (uint32_t)std::min<int64_t>(L.out_cap, std::max(64, atoi(e)));   // (tests: rounds split on output overflow)
+    if (L.sw.out_cap) L.out_cap = (uint32_t)std::min<int64_t>(L.out_cap, L.sw.out_cap);   // (tests: rounds split on output overflow)
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
     L.off_codes = take(L.ltot); L.off_flags = take(L.ltot); L.off_inc4 = take(L.ltot);
@@ -178,7 +180,7 @@ int plan(const sq_batch_desc *d, Layout &L)
         // (measured, whole fold with / without the tables: 10,000 x 300 nt 4.5 / 4.1 ms -- the context kernel costs more than the
         // short walks it replaces --, 1,024 x 1000 nt one fold alone 4.6 / 4.8 (scoring kernel 2.18 / 2.48), two sub-batches side by
         // side 4.45 / 4.2, 1,000 x 2000 nt 27.0 / 29.6: from 800 nt on)
-        const int ctx_min_n = getenv("SQ_CTX_MIN_N") ? atoi(getenv("SQ_CTX_MIN_N")) : 800;
+        const int ctx_min_n = L.sw.ctx_min_n;
         int pt_max = 1;
         for (int j = 0; j < d->njobs; j++)
             pt_max = std::max(pt_max, chain_tcap(d->seq_off[d->job_seq[j] + 1] - d->seq_off[d->job_seq[j]], d->psets[d->job_pset[j]].minlen));
@@ -220,11 +222,11 @@ int plan(const sq_batch_desc *d, Layout &L)
         // kept lists (SQ_BATCH_POOL_LISTS, sequences beyond the scanning round kernel's 256 nt): the counters, a row of page
         // numbers per slot and generation, the pages
         L.kept_pages = 0; L.off_kctr = L.off_kcnt = L.off_ktab = L.off_kpages = 0;
-        if (on && (d->batch_flags & SQ_BATCH_POOL_LISTS) && L.maxn > 256 && L.maxn <= 1024 && !getenv("SQ_NO_POOL_KEPT")) {
+        if (on && (d->batch_flags & SQ_BATCH_POOL_LISTS) && L.maxn > 256 && L.maxn <= 1024 && !L.sw.no_pool_kept) {
             // (pages per slot and generation: measured at 500 nt, 4.0 pages per structure of the largest generation, which fills
             // half of the slots; a list grows with the square of the length)
-            const double pps = getenv("SQ_KEPT_PPS") ? std::max(0.25, atof(getenv("SQ_KEPT_PPS"))) : std::max(1.0, 3.0 * ((double)L.maxn / 500.0) * ((double)L.maxn / 500.0));
-            const double gb = getenv("SQ_KEPT_GB") ? std::max(0.01, atof(getenv("SQ_KEPT_GB"))) : 48.0;
+            const double pps = L.sw.kept_pps > 0 ? L.sw.kept_pps : std::max(1.0, 3.0 * ((double)L.maxn / 500.0) * ((double)L.maxn / 500.0));
+            const double gb = L.sw.kept_gb;
             const double np = std::min((double)sm * pps, gb * 1073741824.0 / 2.0 / (double)SQ_KEPT_PAGE_BYTES);
             L.kept_pages = (uint32_t)std::max(64.0, std::min(np, 4.0e9));
             L.off_kctr = take(256); L.off_kcnt = take(2 * sm * 4); L.off_ktab = take(2 * sm * SQ_KEPT_TAB * 4);
@@ -242,7 +244,7 @@ int plan(const sq_batch_desc *d, Layout &L)
         L.fin_cap = (uint32_t)(want + 2 * (int64_t)d->njobs);
         L.fin_stem_cap = (uint32_t)std::min<int64_t>(std::min<int64_t>(want * std::min(std::max(pt_any / 3, 8), 128), (int64_t)48 << 20) + 2 * L.chain_T,
                                                      (int64_t)0x7FFFFFF0);
-        if (const char *e = getenv("SQ_FIN_STEM_CAP")) L.fin_stem_cap = (uint32_t)std::min<int64_t>(L.fin_stem_cap, std::max(16, atoi(e)));   // (tests: the log's stem room runs out)
+        if (L.sw.fin_stem_cap) L.fin_stem_cap = (uint32_t)std::min<int64_t>(L.fin_stem_cap, L.sw.fin_stem_cap);   // (tests: the log's stem room runs out)
         L.pow_len = 4 * L.maxn + 16;
         const size_t fc = L.fin_cap;
         L.off_fin = take(sizeof(SqPoolFin) * fc); L.off_fin_stems = take(sizeof(SqPoolStem) * (size_t)L.fin_stem_cap);
@@ -316,6 +318,7 @@ extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws,
         }
     }
     sq_batch *b = new sq_batch();
+    b->bsw = L.sw;
     sq_read_fold_switches(b->sw);                           // (every sq_fold refreshes them; the per-call ops read these)
     b->stream = (hipStream_t)hip_stream;
     if (hipGetDevice(&b->device) != hipSuccess) b->device = -1;      // the caller's current device: every thread the library spawns adopts it
@@ -522,13 +525,13 @@ extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws,
         }
     }
     // (not with fp32 score matrices: sq_bits_kernel then derives every job's bits from ITS matrix)
-    const bool no_share = getenv("SQ_NO_SHARED_BITS") != nullptr || b->has_fp32;
+    const bool no_share = b->bsw.no_shared_bits || b->has_fp32;
     std::vector<int64_t> shared_bits((size_t)d->nseq * (size_t)std::max(d->npset, 1), -1);
     for (int j = 0; j < d->njobs; j++) {
         SqJob &J = b->jobs[j];
         const int s = d->job_seq[j];
         J.n = d->seq_off[s + 1] - d->seq_off[s];
-        J.ld = ld_of(J.n); J.seq = s; J.pset = d->job_pset[j];
+        J.ld = ld_of(J.n, b->bsw); J.seq = s; J.pset = d->job_pset[j];
         J.pos_off = d->seq_off[s];
         J.mat64_off = -1; J.has_ext = 0;
         J.nw = bits_nw(J.n); J.bpitch = bits_pitch(J.n);
@@ -822,7 +825,7 @@ extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws,
 extern "C" void sq_batch_destroy(sq_batch *b)
 {
     if (!b) return;
-    static const bool trace = getenv("SQ_PINNED_TRACE") != nullptr;     // (with the cache's trace: a destroy that takes long, by phase)
+    const bool trace = sq_tuning().pinned_trace;     // (with the cache's trace: a destroy that takes long, by phase)
     const double td0 = trace ? now_s() : 0;
     hipStreamSynchronize(b->stream);
     for (int k = 0; k < 4; k++) if (b->side[k]) { hipStreamSynchronize(b->side[k]); sq_stream_put(b->device, b->side[k]); }

@@ -14,6 +14,7 @@
 #include "sq_device.h"
 #include "sq_internal.h"
 #include "sq_tail_dev.h"
+#include "sq_switches.h"
 
 struct HStem {            // host stem record: bps (i+k, j-k), k < len
     int32_t i, j, len;
@@ -107,41 +108,10 @@ struct SqLane {
     std::vector<uint32_t> post_cnt, post_idx, post_fill;   // scratch of the round's output bucketing
 };
 
-// Behaviour switches of a fold, read from the environment ONCE at the start of every sq_fold (and at sq_batch_create, for the
-// per-call ops): diagnostics and test hooks, none changes results; tests flip them between two folds of one process.
-// INTEGRATION.md section 5 documents each.  (Switches that size or shape a batch are read at sq_batch_create; tuning knobs of
-// the launch shapes are `static const`, read once per process where they are used.)
-struct SqFoldSwitches {
-    bool timing = false;              // SQ_TIMING: phase timings on stderr
-    bool pool_debug = false;          // SQ_POOL_DEBUG: pool sizes per round (with SQ_TIMING)
-    bool no_chain = false;            // SQ_NO_CHAIN: poollim = 1 folds driven round by round from the host
-    bool no_rounds = false;           // SQ_NO_ROUNDS: the launched rounds instead of the persistent round kernel
-    bool no_pool = false;             // SQ_NO_POOL: pools booked on the host
-    bool no_opt_chain = false;        // SQ_NO_OPT_CHAIN: pools with a range factor of 1.0 go to the device pools at once (no optimistic chains)
-    bool no_fly_bits = false;         // SQ_NO_FLY_BITS: the bit matrices are always written (the round kernel's scan reads them)
-    bool no_defer_wait = false;       // SQ_NO_DEFER_WAIT: the host waits for the round kernel before it enqueues the device tail
-    bool no_pool_round = false;       // SQ_NO_POOL_ROUND: state / scan / score / choose / extend kernels instead of sq_pool_round_kernel
-    bool pool_round_always = false;   // SQ_POOL_ROUND_ALWAYS: (the default since late round 4; the switch is read and ignored)
-    int pool_round_nsurv = 0;         // SQ_POOL_ROUND_NSURV: survivors sq_pool_round_kernel keeps in LDS (0: by length)
-    int pool_slots = 0;               // SQ_POOL_SLOTS: structure slots the device pools may use (0: max_structs)
-    int pool_root = 0;                // SQ_POOL_ROOT: pools on sequences of 257-1,024 nt run the one-wave round kernel over root lists
-    bool no_pool_kept = false;        // SQ_NO_POOL_KEPT: ... not over the lists their parents left (sq_device.h: SqKept)
-    int pool_ahead = 3;               // SQ_POOL_AHEAD: rounds of the device pools a batch alone enqueues ahead of the host (0: none)
-    int pool_chunk = 0;               // SQ_POOL_CHUNK: structures per chunk of a generation (0: what the arena holds)
-    bool no_score_bound = false;      // SQ_NO_SCORE_BOUND: ScoreStems on every survivor of :492
-    bool no_score_context = false;    // SQ_NO_SCORE_CONTEXT: the strand walk instead of the context tables (launched rounds)
-    bool no_device_algos = false;     // SQ_NO_DEVICE_ALGOS: RunAlgo's edge lists and filters on the host
-    bool no_edges_lds = false;        // SQ_NO_EDGES_LDS: the edges kernel ranks its stems in global memory (the form for lists beyond LDS)
-    bool no_device_tail = false;      // SQ_NO_DEVICE_TAIL: the ranking tail on the host
-    bool algo_sync = false;           // SQ_ALGO_SYNC: matching kernels on the batch stream
-    int lsap_classes = 0;             // SQ_LSAP_CLASSES: size classes of the Hungarian / Nussinov launches (0: 3 crowded, else 1)
-    bool mwm_dump = false;            // SQ_MWM_DUMP: the blossom graphs' sizes and LDS plan on stderr
-    bool mwm_posthoc = false;         // SQ_MWM_POSTHOC: verification of streamed Edmonds results
-};
-void sq_read_fold_switches(SqFoldSwitches &sw);
 
 struct sq_batch {
-    SqFoldSwitches sw;                        // (see above: refreshed by every sq_fold)
+    SqFoldSwitches sw;                        // (sq_switches.h: refreshed by every sq_fold)
+    SqBatchSwitches bsw;                      // (read at sq_batch_create)
     hipStream_t stream = nullptr;
     int device = -1;                          // device current at sq_batch_create (adopted by every spawned thread)
     // host copies

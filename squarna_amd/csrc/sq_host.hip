@@ -5,7 +5,6 @@
 
 static thread_local std::string g_err;
 std::atomic<long long> g_cpuacc[12];
-bool g_cpuacc_on = getenv("SQ_CPUACC") != nullptr;
 
 // host phase timers (printed to stderr when SQ_TIMING is set)
 thread_local double g_t[8];
@@ -57,7 +56,7 @@ int sq_effective_cpus()
             if (FILE *g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) { if (fscanf(g, "%lld", &per) != 1) per = 0; fclose(g); }
             if (quota > 0 && per > 0) cpus = std::min<long long>(cpus, std::max<long long>(1, (quota + per - 1) / per));
         }
-        if (const char *e = getenv("SQ_CPUS")) cpus = std::max(1, atoi(e));
+        if (sq_tuning().cpus) cpus = sq_tuning().cpus;
         return cpus;
     }();
     return n;
@@ -68,7 +67,7 @@ int sq_effective_cpus()
 // relaxed waiting pays once the waiters alone (about two per batch in flight) would take most of the CPU budget
 bool sq_relaxed_waits(const sq_batch *b)
 {
-    static const int forced = getenv("SQ_RELAX") ? atoi(getenv("SQ_RELAX")) : -1;
+    const int forced = sq_tuning().relax;
     if (forced >= 0) return forced != 0;
     int lws = 1;
     if (const char *e = getenv("LOCAL_WORLD_SIZE")) lws = std::max(1, atoi(e));
@@ -182,7 +181,7 @@ SqPool *sq_pool(sq_batch *b)
         unsigned cores = (unsigned)sq_effective_cpus();
         if (const char *lws = getenv("LOCAL_WORLD_SIZE")) cores = std::max(1u, cores / (unsigned)std::max(1, atoi(lws)));
         int nthr = (int)std::min(std::max(4u * cores / (unsigned)std::max(1, b->inflight), 8u), 32u);
-        if (const char *e = getenv("SQ_HOST_THREADS")) nthr = std::max(1, atoi(e));
+        if (b->bsw.host_threads) nthr = b->bsw.host_threads;
         b->pool = sq_pool_get(nthr, b->device);
     }
     return b->pool;
@@ -308,7 +307,7 @@ int sq_pinned_get(void **p, size_t bytes)
         }
     }
     // portable: the cache is process-wide, a buffer may be reused by a batch on another device
-    static const bool trace = getenv("SQ_PINNED_TRACE") != nullptr;      // (one line per trip to the driver)
+    const bool trace = sq_tuning().pinned_trace;      // (one line per trip to the driver)
     const double tm0 = trace ? now_s() : 0;
     const int r = sq_check(hipHostMalloc(p, want, hipHostMallocCoherent | hipHostMallocMapped | hipHostMallocPortable), "hipHostMalloc");
     if (trace) fprintf(stderr, "[sq_pinned] hipHostMalloc %zu bytes: %.2f ms (idle %zu buffers, %zu MB)\n", want, (now_s() - tm0) * 1e3, g_pinned.idle.size(), g_pinned.idle_bytes >> 20);
@@ -321,7 +320,7 @@ void sq_pinned_put(void *p)
 {
     // idle buffers kept: two steps' worth of a server that builds the next batches while it folds (16 batches of 12 SRtest150
     // sets pin ~3 GB between them); SQ_PINNED_CACHE_MB overrides
-    static const size_t kIdleBytes = (size_t)(getenv("SQ_PINNED_CACHE_MB") ? std::max(0, atoi(getenv("SQ_PINNED_CACHE_MB"))) : 6144) << 20;
+    static const size_t kIdleBytes = (size_t)sq_tuning().pinned_cache_mb << 20;
     static const size_t kIdleCount = 4096;
     if (!p) return;
     std::vector<void *> drop;
@@ -346,7 +345,7 @@ void sq_pinned_put(void *p)
             p = nullptr;
         }
     }
-    static const bool trace = getenv("SQ_PINNED_TRACE") != nullptr;
+    const bool trace = sq_tuning().pinned_trace;
     if (trace && (!drop.empty() || p)) fprintf(stderr, "[sq_pinned] hipHostFree x %zu\n", drop.size() + (p ? 1 : 0));
     for (void *q : drop) hipHostFree(q);
     if (p) hipHostFree(p);

@@ -1,7 +1,8 @@
 // sq_host_int.h -- what the host-side translation units of the library share beyond sq_host.h: sq_host.hip (errors, worker
 // pools, stream / event / pinned-buffer caches, profiling), sq_batch.hip (workspace layout, sq_batch_create / destroy),
 // sq_round_host.hip (the launches of a round, the host-driven round driver, the per-call C ABI of a-1 .. a-6, alignment
-// step 1), sq_fold.hip (sq_fold and the concurrent forms), sq_results.hip (result getters and packing).
+// step 1), sq_fold.hip (sq_fold and the concurrent forms; with sq_fold_chain.hip, sq_fold_pool.hip: sq_fold_run.h),
+// sq_results.hip (result getters and packing), sq_switches.cpp (the SQ_* environment switches: sq_switches.h).
 #pragma once
 #include <algorithm>
 #include <atomic>

@@ -46,7 +46,7 @@ void sq_max_dynamic_lds(const void *fn, int bytes);      // sq_host.hip: once pe
 int sq_launch_matching(int algo, const SqMatchJob *h_jobs, int nj, const SqMatchJob *jobs, const SqMatchEdge *edges,
                        size_t nedges, SqMatchEdge *dev_edges, char *d_scr, int32_t *out, int32_t *cnt,
                        const uint8_t *codes, uint32_t *job_flags, uint32_t flag_val, hipStream_t st,
-                       SqMatchJob *jobs_rw = nullptr, int32_t *bin_head = nullptr, int inflight = 1);
+                       SqMatchJob *jobs_rw = nullptr, int32_t *bin_head = nullptr, int inflight = 1, bool dump = false);
 extern "C" {
 __global__ void sq_lsap_kernel(const SqMatchJob *jobs, const SqMatchEdge *edges, char *scratch, int32_t *col4row_out,
                                int lds_bytes);

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include "sq_match.h"
+#include "sq_switches.h"
 #include "sq_hostflag.h"
 #include <vector>
 #include <algorithm>
@@ -491,12 +492,12 @@ extern "C" __global__ void sq_flag_kernel(uint32_t *flag, uint32_t value)
 //     150 KB -> 48 KB from three batches in flight on.  SQ_MWM_BIN_WAVES / SQ_MWM_BIN_BYTES / SQ_MWM_ALL_CAP override.
 // Writes lds_off / lds_bytes / next of jobs_rw (the table the kernel reads) and bin_head[0..nbins).
 void sq_mwm_plan(const SqMatchJob *h_jobs, SqMatchJob *jobs_rw, int nj, int32_t *bin_head, int inflight, int &nbins, int &waves,
-                 size_t &lds, bool &all_in_lds)
+                 size_t &lds, bool &all_in_lds, bool dump)
 {
-    static const int env_waves = getenv("SQ_MWM_BIN_WAVES") ? atoi(getenv("SQ_MWM_BIN_WAVES")) : 0;
-    static const long env_cap = getenv("SQ_MWM_BIN_BYTES") ? atol(getenv("SQ_MWM_BIN_BYTES")) : 0;
-    static const long env_all = getenv("SQ_MWM_ALL_CAP") ? atol(getenv("SQ_MWM_ALL_CAP")) : 0;
-    static const bool nolds = getenv("SQ_MWM_NOLDS") != nullptr;
+    const SqTuning &tu = sq_tuning();
+    const int env_waves = tu.mwm_bin_waves;
+    const long env_cap = tu.mwm_bin_bytes, env_all = tu.mwm_all_cap;
+    const bool nolds = tu.mwm_nolds;
     const size_t hdr = (sizeof(SqBlossom) + 15) & ~(size_t)15;
     const bool many = inflight >= 3;
     // A launch (or the launches in flight together) with more graphs than the chip has room for at one graph per CU is a
@@ -548,7 +549,7 @@ void sq_mwm_plan(const SqMatchJob *h_jobs, SqMatchJob *jobs_rw, int nj, int32_t 
         while (first_open < used.size() && cnt[first_open] >= waves) first_open++;
     }
     lds = (lds + 255) & ~(size_t)255;
-    if (getenv("SQ_MWM_DUMP")) {
+    if (dump) {
         size_t tot = 0; int nfull = 0;
         for (int q = 0; q < nj; q++) { tot += need[q]; nfull += need[q] > hdr + SqBlossom::hot_bytes(h_jobs[q].n, h_jobs[q].nedges, 2) + 32; }
         fprintf(stderr, "[mwm plan] %d graphs (inflight %d): %d bins of <= %d waves, %zu B of LDS per block, %zu B needed in all, %d graphs fully in LDS\n",
@@ -559,7 +560,7 @@ void sq_mwm_plan(const SqMatchJob *h_jobs, SqMatchJob *jobs_rw, int nj, int32_t 
 int sq_launch_matching(int algo, const SqMatchJob *h_jobs, int nj, const SqMatchJob *jobs, const SqMatchEdge *edges,
                        size_t nedges, SqMatchEdge *dev_edges, char *d_scr, int32_t *out, int32_t *cnt,
                        const uint8_t *codes, uint32_t *job_flags, uint32_t flag_val, hipStream_t st,
-                       SqMatchJob *jobs_rw, int32_t *bin_head, int inflight)
+                       SqMatchJob *jobs_rw, int32_t *bin_head, int inflight, bool dump)
 {
     int maxn = 0, maxm = 0;
     for (int q = 0; q < nj; q++) { maxn = maxn > h_jobs[q].n ? maxn : h_jobs[q].n; maxm = maxm > h_jobs[q].nedges ? maxm : h_jobs[q].nedges; }
@@ -576,7 +577,7 @@ int sq_launch_matching(int algo, const SqMatchJob *h_jobs, int nj, const SqMatch
         // through the single-threaded BackTrack too)
         // (with the chip crowded ONE wave per job: a block of three waves holds three wave slots through every barrier-separated
         // diagonal, and wave slots are what a crowded chip runs out of -- a lane then takes up to three cells of a diagonal)
-        static const int env_thr = getenv("SQ_NUSS_THREADS") ? std::max(64, std::min(256, atoi(getenv("SQ_NUSS_THREADS")) / 64 * 64)) : 0;
+        const int env_thr = sq_tuning().nuss_threads;
         // ... and so is a launch of hundreds of LARGE graphs (hot part beyond a crowd's 40 KB bin: 500 vertices and 17,000 edges take
     // 50 KB) beside the rounds of the same batch's pools: 822 such graphs fill the LDS of every CU for 75 ms, during which the
     // round kernel does not run (round 6: 1,000 records of 500 nt under pools of a thousand 313 -> 278 ms with the graphs' state
@@ -589,7 +590,7 @@ int sq_launch_matching(int algo, const SqMatchJob *h_jobs, int nj, const SqMatch
     } else {                                             // SQ_ALGO_E
         // bins: see sq_mwm_plan.  The plan writes each job's LDS slice into the job table the kernel reads.
         int nbins = 0, waves = 1; size_t lds = 0; bool all_in_lds = true;
-        sq_mwm_plan(h_jobs, jobs_rw, nj, bin_head, inflight, nbins, waves, lds, all_in_lds);
+        sq_mwm_plan(h_jobs, jobs_rw, nj, bin_head, inflight, nbins, waves, lds, all_in_lds, dump);
         sq_max_dynamic_lds((const void *)sq_mwm_kernel, 156 * 1024);
         if (!all_in_lds && dev_edges != edges) {
             // some job keeps its adjacency in global memory and walks the edges in place: give the launch a device copy

@@ -24,7 +24,7 @@ int sq_fill_impl(sq_batch *b, int full)
             // its blocks are fewer and fatter than the generic path's so that the staging is amortised
             const bool lds_inputs = b->maxn <= 4096;
             // 16-byte stores per thread: as many as leave ~4096 blocks in the launch (the LDS staging of a block is amortised over them)
-            static const int fper_env = getenv("SQ_FILL_PER") ? atoi(getenv("SQ_FILL_PER")) : 0;
+            const int fper_env = sq_tuning().fill_per;
             const int64_t fper = 256 * (fper_env > 0 ? (int64_t)fper_env
                                                      : std::min<int64_t>(std::max<int64_t>(maxq * nj / (256 * 4096), 4), 64));
             const size_t fdyn = lds_inputs ? (size_t)12 * ((b->maxn + 15) & ~15) + 64 : 0;
@@ -32,7 +32,7 @@ int sq_fill_impl(sq_batch *b, int full)
             hipLaunchKernelGGL(sq_fill_kernel, fgrid, dim3(256), fdyn, b->stream, c, full ? 0 : 1, b->mul_applied ? 1 : 0);
         }
         if (any_ext1) hipLaunchKernelGGL(sq_import_kernel, grid, dim3(256), 0, b->stream, c);
-        if (full && !getenv("SQ_BITS_DIRECT")) hipLaunchKernelGGL(sq_bits_kernel, grid, dim3(256), 0, b->stream, c, 0);
+        if (full && !b->bsw.bits_direct) hipLaunchKernelGGL(sq_bits_kernel, grid, dim3(256), 0, b->stream, c, 0);
         else {
             if (any_ext1) hipLaunchKernelGGL(sq_bits_kernel, grid, dim3(256), 0, b->stream, c, 1);
             dim3 g2((unsigned)std::min<int64_t>(std::max<int64_t>(maxw, 1), 2048), (unsigned)nj);
@@ -42,7 +42,7 @@ int sq_fill_impl(sq_batch *b, int full)
             // letter-mask formulation unless the chain test is on or the O(N) tables outgrow LDS
             const int nwmax = (b->maxn + 31) / 32;
             const size_t mdyn = 3 * (size_t)((b->maxn + 3) & ~3) + 4 * (size_t)b->nletters * (nwmax + 3) + 4 * (size_t)nwmax * b->nletters + 16;
-            static const bool no_masks = getenv("SQ_BITS_NOMASKS") != nullptr;
+            const bool no_masks = sq_tuning().bits_nomasks;
             if (!b->interchainonly && !no_masks && b->nletters > 0 && mdyn <= 60 * 1024) {
                 const int bparts = std::max(1, std::min(nwmax, (2048 + nj - 1) / nj));
                 hipLaunchKernelGGL(sq_bits_masks_kernel, dim3(bparts, nj), dim3(256), mdyn, b->stream, c, b->nletters);
@@ -220,10 +220,8 @@ void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64
 {
     const bool crowded = b->inflight > 1 || b->njobs >= 4096;    // (by the batch, not by the launch: a batch's rounds all run one way)
     // short sequences on a crowded chip: state and scan in one launch, one wave per structure (sq_state_scan_kernel)
-    static const bool no_fuse = getenv("SQ_NO_STATE_SCAN_FUSE") != nullptr;
-    static const int st_short_env = getenv("SQ_STATE_SHORT_THREADS") ? atoi(getenv("SQ_STATE_SHORT_THREADS")) : 64;
-    static const int sc_short_env = getenv("SQ_SCAN_SHORT_WAVES") ? atoi(getenv("SQ_SCAN_SHORT_WAVES")) : 1;
-    const bool fuse = crowded && maxn <= 200 && maxn >= 5 && !no_fuse && st_short_env == 64 && sc_short_env == 1;
+    const SqTuning &tu = sq_tuning();
+    const bool fuse = crowded && maxn <= 200 && maxn >= 5 && !tu.no_state_scan_fuse && !tu.state_short_set && !tu.scan_short_set;
     // the pools' short structures: extension + state + scan + score + choose of a structure by ONE wave in ONE launch
     // (sq_pool_round.hip; pool_fold decides per fold and then launches no extend kernel)
     if (pool_round) {
@@ -239,7 +237,7 @@ void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64
         // (the structure records go to the device by ONE copy first: read from the pinned array by every wave, each of the
         // launch's thousands of waves began with a read over PCIe -- 3.0 -> 1.2 G wave cycles per three headline steps,
         // the headline +1.6 %; SQ_NO_STATE_COPY: the old form)
-        static const bool copy_first = getenv("SQ_NO_STATE_COPY") == nullptr;
+        const bool copy_first = !tu.no_state_copy;
         SqRoundIO io2 = io;
         if (copy_first && !chained && io.h_structs != io.d_structs) {
             hipMemcpyAsync(io.d_structs, io.h_structs, (size_t)S * sizeof(SqStruct), hipMemcpyHostToDevice, st);
@@ -258,7 +256,7 @@ void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64
         // jobs and more (a 219-record batch alone -- 1,095 jobs -- keeps its rounds a latency chain).  Then a short structure gets ONE wave in the state, scan and scoring kernels; a small batch
         // alone keeps the wide blocks (its greedy rounds are a latency chain: one wave per structure made them 1.5 ms
         // longer per 219-record fold, hidden behind the blossom kernel only when there is one)
-        static const int state_short = getenv("SQ_STATE_SHORT_THREADS") ? std::max(64, std::min(256, atoi(getenv("SQ_STATE_SHORT_THREADS")) / 64 * 64)) : 64;
+        const int state_short = tu.state_short_threads;
         hipLaunchKernelGGL(sq_state_kernel, dim3(S), dim3(maxn <= 200 && crowded ? state_short : 256), st_dyn, st, b->ctx, io, b->state, scan, st_lds_n, chained ? 1 : 0);
     }
     // mode 0: the context tables of the round's structures (only long-sequence batches carry them)
@@ -268,7 +266,7 @@ void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64
         ProfScope ps(b, 2, scan_bytes);
         // bit-diagonal scan: one wave = 64 anti-diagonals
         // (sequences up to 200 nt: one wave per structure walks all its diagonal groups, see the kernel)
-        static const int scan_short = getenv("SQ_SCAN_SHORT_WAVES") ? std::max(1, atoi(getenv("SQ_SCAN_SHORT_WAVES"))) : 1;
+        const int scan_short = tu.scan_short_waves;
         const int scan_groups = (2 * maxn - 5 + 63) / 64 + 1;
         hipLaunchKernelGGL(sq_scan6_kernel, dim3(S, maxn <= 200 && crowded ? std::min(scan_short, scan_groups) : scan_groups), dim3(64), 4 * (size_t)b->state.fbstride, st,
                            b->ctx, d_structs, b->state, scan);
@@ -277,20 +275,18 @@ void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64
         ProfScope ps(b, 3, 0);
         // dynamic LDS: letter codes of the longest sequence, plus its reactivities when they fit in 32 KiB
         const int lds_n = maxn <= 16384 ? maxn : 0;
-        static const int nr_lim = getenv("SQ_SCORE_NR_LIM") ? atoi(getenv("SQ_SCORE_NR_LIM")) : 4096;
+        const int nr_lim = tu.score_nr_lim;
         // (only when some job needs them: sequences whose reactivities go through the cell table leave the room to the
         // partner / prefix arrays -- S2000 with encoded SHAPE: 16 KB that pushed those arrays out to global memory)
         const int lds_nr = need_reacts && maxn <= nr_lim ? maxn : 0;
         // partner / prefix arrays (3 x int16) too, while a block stays small enough for four blocks per CU
         // (the reactivity case is bound by fp64 sqrt/div throughput and prefers the occupancy)
-        static const size_t state_lim = getenv("SQ_SCORE_STATE_LIM") ? (size_t)atol(getenv("SQ_SCORE_STATE_LIM")) : 24 * 1024;
+        const size_t state_lim = tu.score_state_lim;
         const size_t dyn_base = lds_n ? (size_t)((lds_n + 15) & ~15) + (size_t)8 * lds_nr + 16 : 0;
         const int lds_ns = (lds_n && mode == 0 && dyn_base + (size_t)6 * ((maxn + 8) & ~7) <= state_lim) ? maxn : 0;
         size_t dyn = lds_n ? (size_t)((lds_n + 15) & ~15) + (size_t)8 * lds_nr + (size_t)6 * ((lds_ns + 8) & ~7) + 16 : 0;
         // few structures: deal each structure's candidates to several blocks so that the launch still fills the chip
-        static const int score_threads = getenv("SQ_SCORE_THREADS") ? atoi(getenv("SQ_SCORE_THREADS")) : 0;
-        static const int score_parts = getenv("SQ_SCORE_PARTS") ? atoi(getenv("SQ_SCORE_PARTS")) : 0;
-        static const int score_target = getenv("SQ_SCORE_TARGET") ? atoi(getenv("SQ_SCORE_TARGET")) : 512;
+        const int score_threads = tu.score_threads, score_parts = tu.score_parts, score_target = tu.score_target;
         // mode 0 (two-phase loop): ~512 blocks of 512 threads; the one-pass modes want many small blocks in flight
         int parts = std::max(1, std::min({512, ((mode == 0 ? score_target : 4096) + S - 1) / S, (int)(maxcap / 1024)}));
         if (score_parts) parts = score_parts;
@@ -298,10 +294,10 @@ void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64
         // short ones leave half of such a block idle behind its set-up (n = 300: 10,000 chains 5.9 -> 4.6 ms, pools
         // of a thousand 24 -> 16 ns per structure and round with 256).  SRtest150 (up to ~500 nt) measures the same
         // either way within the run-to-run spread and keeps 512.
-        static const int short_thr = getenv("SQ_SCORE_SHORT_THREADS") ? atoi(getenv("SQ_SCORE_SHORT_THREADS")) : 64;
+        const int short_thr = tu.score_short_threads;
         // (the pools' generations of thousands of structures: most of them late in their fold, with one or two thousand candidates
         // left -- 500nobpp on 500-nt sequences: 382 / 315 / 301 ms per 500 sequences with 512 / 256 / 128 threads)
-        const int pooled_thr = getenv("SQ_SCORE_POOL_THREADS") ? std::max(64, std::min(1024, atoi(getenv("SQ_SCORE_POOL_THREADS")) / 64 * 64)) : 128;
+        const int pooled_thr = b->sw.score_pool_threads;
         const int thr0 = maxn <= 200 ? (crowded ? short_thr : 128) : (pooled && S >= 2048 ? std::min(pooled_thr, maxn <= 400 ? 256 : 512) : (maxn <= 400 ? 256 : 512));
         // (the one-pass modes on a crowded chip: a structure of a short sequence has ~150 candidates -- one wave, not four)
         const int thr = score_threads ? score_threads : (mode == 0 ? thr0 : (maxn <= 200 && crowded ? 64 : (parts == 1 && S < 2048 ? 512 : 256)));
@@ -334,7 +330,7 @@ void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64
         if (pooled) {
             // survivors within subopt x best the choose kernel sorts in LDS (18 bytes each): 1,024 for long sequences, 384 up to
             // 200 nt (measured on SRtest150 under nobpp / alt / greedynobpp: at most a few dozen are ever in range)
-            static const int short_surv = getenv("SQ_POOL_SHORT_NSURV") ? std::max(64, std::min(1024, atoi(getenv("SQ_POOL_SHORT_NSURV")))) : 384;
+            const int short_surv = tu.pool_short_nsurv;
             const int nsurv = maxn <= 200 ? short_surv : 1024;
             hipLaunchKernelGGL(sq_pool_choose_kernel, dim3(S), dim3(64), (size_t)18 * nsurv + 16, st, b->ctx, d_structs, scan, b->pool_io, nsurv);
         }
@@ -381,7 +377,7 @@ static int run_chunk(sq_batch *b, SqLane &ln, const std::vector<SView> &structs,
             HIPCK(hipMemcpyAsync(d_cols, sink->cols + c0, (size_t)(c1 - c0) * 4, hipMemcpyHostToDevice, st));
             // order-free chunk (dyadic weights, no reactivity factors, no caller matrices): every sum is exact, so one
             // launch with atomic adds gives the same bits as the sequential order
-            static const bool no_atomic = getenv("SQ_ALIGN_SEQUENTIAL") != nullptr;
+            const bool no_atomic = sq_tuning().align_sequential;
             bool order_free = !no_atomic;
             int64_t maxcap = 1;
             for (int k = 0; k < S && order_free; k++) {

@@ -106,15 +106,14 @@ def test_persistent_rounds_on_the_baseline_shapes(n, count, seed, reacts):
 
 # ---- device pools: a round of short structures as ONE kernel (sq_pool_round.hip) ---------------------------------------
 def _pools_both_ways(prepared, psets, env=None, **kw):
-    """Packed records of one batch folded with sq_pool_round_kernel (forced: SQ_POOL_ROUND_ALWAYS) and with the launched
-    state / scan / score / choose kernels (SQ_NO_POOL_ROUND)."""
+    """Packed records of one batch folded with sq_pool_round_kernel (the default) and with the launched state / scan / score /
+    choose kernels (SQ_NO_POOL_ROUND)."""
     from squarna_amd.engine import Batch, pool_slot_cap, pool_slots_wanted_many
     out = []
     lengths = [len(p.shortseq) for p in prepared]
     slots = int(min(pool_slots_wanted_many(lengths, psets, kw.get("poollim", 1000)).sum(), pool_slot_cap(max(lengths))))
     for launched in (False, True):
-        extra = dict(env or {}) if not launched else {}
-        extra["SQ_NO_POOL_ROUND" if launched else "SQ_POOL_ROUND_ALWAYS"] = "1"
+        extra = dict(env or {}) if not launched else {"SQ_NO_POOL_ROUND": "1"}
         assert not any(k in os.environ for k in extra)
         os.environ.update(extra)
         try:

@@ -5,7 +5,8 @@ reference.  Single-sequence predictions are batched across the input records and
 the GPU (the reference parallelises the same loop over CPU processes, SQUARNA.py:887-935);
 blocks are printed in input order; alignment mode (``a``) runs through ``squarna_amd.align``.
 ``bpp != 0`` paramsets take their base-pair probabilities from ViennaRNA on the host (``import RNA``,
-as the reference does).  Out of scope of this build: Rfam/G4/RBP restraint discovery.
+as the reference does).  ``g4`` / ``rbp`` restraint discovery for a single input record runs on the host
+(``squarna_amd.motifs``).  Out of scope of this build: Rfam restraint discovery (``rfam``).
 """
 import io
 import os
@@ -146,8 +147,8 @@ def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
 
     if alignment and not configfileset:                          # SQUARNA.py:822-824
         configfile = os.path.join(HOME_DIR, "ali.conf")
-    if rfam or g4 or rbp:
-        raise NotImplementedError("Rfam / G4 / RBP restraint discovery (SQRNrfam.py) is out of scope of this build")
+    if rfam:
+        raise NotImplementedError("Rfam restraint discovery (Infernal's cmscan, SQRNrfam.py) is out of scope of this build")
 
     paramsetnames, paramsets = ParseConfig(configfile)
     if not configfileset:
@@ -188,6 +189,16 @@ def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
                       threads, rankbydiff, rankby, hardrest, interchainonly, toplim, outplim, conslim, reactformat,
                       poollim, entropy=entropy, algos=algos, sink=write_to, M=M, B=B)
         return
+    rfamlabel = False                                            # SQUARNA.py:850-866: G4 / RBP restraints, one record only
+    if g4 or rbp:
+        if not single_input:
+            print("WARNING: Found more than one sequence, rfam/G4/RBP search disabled.", file=sys.stderr)
+        elif _select is None or 0 in _select:
+            from .motifs import SearchG4RBP
+            inputs = [list(rec) for rec in inputs]
+            found, rfamlabel = SearchG4RBP(inputs[0][1], g4, rbp)
+            if found:
+                inputs[0][3] = found                             # (replaces any restraint line of the input)
 
     def config_for(seq):                                        # autoconfig, SQUARNA.py:868-878
         if configfileset:
@@ -213,10 +224,11 @@ def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
             groups = {}
             for k, rec in enumerate(batch):
                 names = rec[5]
-                groups.setdefault(tuple(sorted(resolve_priority(priority, names))), []).append(k)
+                groups.setdefault(tuple(sorted(resolve_priority(priority, names, rfamlabel))), []).append(k)
             # The library writes the output blocks itself (sq_write_blocks) when the engine can: the records then carry their
-            # block fields (name, encoded reactivity line, which list of paramset names they print)
-            blocks = getattr(eng, "writes_blocks", False)
+            # block fields (name, encoded reactivity line, which list of paramset names they print).  Not a record with G4 /
+            # RBP restraints (rfamlabel: the only record of its input): its block carries the label and the '+' marks.
+            blocks = getattr(eng, "writes_blocks", False) and not rfamlabel
             psnames, psname_idx = [], {}
             for prio, idx in groups.items():
                 if blocks:
@@ -259,7 +271,7 @@ def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
             RunSQRNdbnseq(name, seq, reacts, restrs, ref, names, psets, threads, rankbydiff, rankby,
                           hardrest, interchainonly, toplim, outplim, conslim, reactformat, evalonly, poollim,
                           mp=False, sink=sink, entropy=entropy, algos=algos, levellimit=levellimit,
-                          priority=priority, rfam=False, M=M, B=B, _prediction=preds[k], _ref_scores=refsc[k])
+                          priority=priority, rfam=rfamlabel, M=M, B=B, _prediction=preds[k], _ref_scores=refsc[k])
             if _on_block:
                 _on_block(index, sink.getvalue())
 

@@ -8,6 +8,8 @@
 #define SQ_PR_STAGE 128            // runs the scan stages in LDS before they are scored (64 at a time)
 #endif
 #define SQ_PR_ROOT_MAXN 1024       // ... with root lists (SqPoolRoundArgs::root)
+#define SQ_PR_WQ 128               // (root lists) the walks' queue: runs that passed :492 without a finalscore, 16 bytes each
+#define SQ_PR_WQ_SURV 88           // ... it takes the room of this many survivors at the end of the survivors' tail
 #define SQ_PR_MAXN 256             // longest sequence the kernel takes (one wave per structure; measured to 1,024: parity clean, no faster than the launched round kernels from ~300 nt on -- a round of long structures is bound by its scan and ScoreStems work, not by launches)
 
 struct SqPoolRoundArgs {
@@ -62,6 +64,9 @@ __host__ __device__ inline SqPoolRoundLds sq_pool_round_lds(int lds_n, int str_c
     L.off_surv = o;
     L.choose_cap = L.off_stems / 16 < 512 ? L.off_stems / 16 : 512;   // (the stems stay: a final structure logs them)
     size_t tail = (size_t)24 * surv_cap + 16;              // bpscore, finalscore, key, length, place in the structure's kept list
+    // (root lists: surv_cap - SQ_PR_WQ_SURV survivors, then the walks' queue from the next 16 bytes -- 24 x survivors is a
+    // multiple of 8, so at most 8 bytes of padding)
+    static_assert(24 * SQ_PR_WQ_SURV + 16 - 8 >= 16 * SQ_PR_WQ, "the walks' queue must fit in the survivors' tail");
     const size_t ext = (size_t)8 * L.t8 + 64 * 4 + 64 + 16;   // crossing weights (int32), order, group, level, group sizes, ranks
     if (SQ_PR_STAGE * 8 + tail < ext) tail = ext - SQ_PR_STAGE * 8;
     L.total = (size_t)o + tail;

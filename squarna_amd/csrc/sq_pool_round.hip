@@ -467,12 +467,18 @@ __device__ __forceinline__ void sq_pool_round_body(const SqDevCtx &c, const SqSc
         const double subopt = st.subopt;
         // the survivors' room: the runs within range (SqPrSurv, a shorter list), behind them the walks' queue
         struct WQ { uint32_t key, lp; double bps; };                              // lp: length | place in this structure's list << 16
-        sv.cap = ra.surv_cap - 88;
+        sv.cap = ra.surv_cap - SQ_PR_WQ_SURV;
         sv.bps = reinterpret_cast<double *>(pr_dyn + Lo.off_surv); sv.fin = sv.bps + sv.cap;
         sv.key = reinterpret_cast<uint32_t *>(sv.fin + sv.cap); sv.len = reinterpret_cast<uint16_t *>(sv.key + sv.cap);
         sv.place = sv.len + sv.cap;
-        WQ *const wq = reinterpret_cast<WQ *>(pr_dyn + Lo.off_surv + (((size_t)24 * sv.cap + 15) & ~(size_t)15));   // 128 entries
+        static_assert(sizeof(WQ) == 16, "sq_pool_round_lds sizes the walks' queue in 16-byte entries");
+        // (SQ_PR_WQ entries: at most 63 wait when 64 more arrive -- every step of the stream serves the walks before the cuts,
+        // and every step of serve_cuts serves them after its own enqueue.  A wave of entries beyond the room of this queue or
+        // of the cut runs' is dropped, and the pools overflow into the host's loop once the stream is done: qfull is
+        // wave-uniform, one flag instead of a store in every enqueue -- the kernel spills at its 168 registers)
+        WQ *const wq = reinterpret_cast<WQ *>(pr_dyn + Lo.off_surv + (((size_t)24 * sv.cap + 15) & ~(size_t)15));
         uint32_t nwq = 0;
+        bool qfull = false;
         // the pages this structure's list will need, in one go (it is at most as long as its source, pieces of cut runs aside: those
         // take further pages one by one) -- a returning atomic per page was a trip to memory every fourth step
         if (mylist && R > 0u) {
@@ -540,8 +546,10 @@ __device__ __forceinline__ void sq_pool_round_body(const SqDevCtx &c, const SqSc
                 if (ub < minfin || (anybest && ub < subopt * best)) want = false;    // no reader of the list can use it
             }
             const unsigned long long m = __ballot(want);
+            const uint32_t to = nwq + (uint32_t)__popcll(m);
+            if (to > (uint32_t)SQ_PR_WQ) { qfull = true; return; }
             if (want) wq[nwq + (uint32_t)__popcll(m & below)] = WQ{key, (uint32_t)L | (place << 16), bps};
-            nwq += (uint32_t)__popcll(m);
+            nwq = to;
         };
         auto serve_walks = [&](bool all) {
 #ifdef SQ_PR_PROF
@@ -674,14 +682,19 @@ __device__ __forceinline__ void sq_pool_round_body(const SqDevCtx &c, const SqSc
 #ifdef SQ_PR_PROF
                 _ncutrun += __popcll(m);
 #endif
-                if (cutrun) cutq[ncq + (uint32_t)__popcll(m & below)] = make_uint2(rkey, (uint32_t)L);
-                ncq += (uint32_t)__popcll(m);
+                const uint32_t cto = ncq + (uint32_t)__popcll(m);
+                if (cto > (uint32_t)SQ_PR_STAGE) qfull = true;
+                else {
+                    if (cutrun) cutq[ncq + (uint32_t)__popcll(m & below)] = make_uint2(rkey, (uint32_t)L);
+                    ncq = cto;
+                }
+                if (nwq >= 64u) serve_walks(false);                             // (first: serve_cuts enqueues up to 64 walks a step)
                 if (ncq >= 64u) serve_cuts(false);
-                if (nwq >= 64u) serve_walks(false);
             }
         }
         serve_cuts(true);
         serve_walks(true);
+        if (qfull && lane == 0) *sv.pool_ovf = 1;
 #undef SQ_OV
         if (K.on && lane == 0) {
             K.cnt[krow] = mylist ? mycnt : SQ_KEPT_NOLIST;

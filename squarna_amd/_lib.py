@@ -176,7 +176,7 @@ CAP_CANDIDATES, CAP_STRUCTS, CAP_OUTPUT, CAP_FIXED = 1, 2, 3, 4      # sq_last_c
 class CapacityError(RuntimeError):
     """A capacity the batch was created with (candidate records per structure, the log of final structures) did not hold the
     fold: status -3 of the C ABI.  `kind` is sq_last_capacity()'s answer -- which capacity --, so that the engine can repeat
-    the fold with a larger batch (engine.HipEngine._fold_groups) without reading the message."""
+    the fold with a larger batch (engine.HipEngine._fold_with_retry) without reading the message."""
 
     def __init__(self, msg, kind=0):
         super().__init__(msg)

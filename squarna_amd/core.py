@@ -3,7 +3,7 @@
 Same names, argument meaning and return shapes as ``src/SQUARNA/SQRNdbnseq.py``:
 ``BPMatrix`` (:258), ``AnnotateStems`` (:427), ``OptimalStems`` (:792), ``SQRNdbnseq`` (:973),
 ``RunSQRNdbnseq`` (:1289).  All arithmetic of the hot path runs on the GPU through
-libsquarna_hip.so (see engine.py); this module only converts Python records and prints.
+libsquarna_hip.so (see engine.py and batch.py); this module only converts Python records and prints.
 """
 import sys
 
@@ -42,7 +42,7 @@ def BPMatrix(seq, weights, rxs, rlefts, rrights, interchainonly=False, reacts=No
              M=1.8, B=-0.6):
     """(bpboolmatrix, bpscorematrix), dense N x N float64 -- SQRNdbnseq.py:258-367.
     Computed on the GPU in fp64 (sq_bpmatrix_read).  bpp_power != 0 takes ViennaRNA's base-pair
-    probabilities from the host (engine.vienna_bpp, i.e. `import RNA`); the term (bppm/max)**|p| is uploaded
+    probabilities from the host (bpp.vienna_bpp, i.e. `import RNA`); the term (bppm/max)**|p| is uploaded
     with the batch and the fill kernel applies it on the device: scoremat *= term (p > 0) or += term (p < 0)
     (SQRNdbnseq.py:350-364)."""
     n = len(seq)

@@ -7,7 +7,7 @@ made with which arguments, the ``max == 0`` rescale retry (:355-364), the skip w
 all zero, and the application ``scoremat *= (bpp/max)**p`` / ``+= (bpp/max)**-p`` plus all five
 algorithms downstream.  ``tests/golden/gen_bpp_golden.py`` installs this module as ``RNA`` and runs the
 REAL reference on it; the GPU tests install the same module and run the product
-(``engine.vienna_bpp`` does its own ``import RNA``), so both sides see identical "probabilities".
+(``bpp.vienna_bpp`` does its own ``import RNA``), so both sides see identical "probabilities".
 
 The fake is a pure function of what the caller handed over:
   * the sequence given to ``fold_compound`` (after the reference's N-substitution, :343-344),

@@ -6,6 +6,7 @@ import numpy as np
 
 from . import _lib
 from .dbn import DBNToPairs, encode_seq
+from .plan import workspace_size_class
 from .records import PackedRows
 from .results import unpack_result, _metrics, _MASK_IDS, _Blocks
 
@@ -57,16 +58,18 @@ class Batch:
         if isinstance(prepared, PackedRows):
             # an alignment's rows as arrays (no per-row records: the batch computes, it has no results to decode)
             pk, prepared = prepared, None
-            nseq, ltot = pk.nseq, int(pk.seq_off[-1])
+            nseq = pk.nseq
             self.prepared = None
             self.seq_off, self.codes, self.flags, self.reacts, self.rbp_off, self.rbps = pk.seq_off, pk.codes, pk.flags, pk.reacts, pk.rbp_off, pk.rbps
         else:
-            nseq, ltot = self._host_arrays(prepared)
+            nseq = self._host_arrays(prepared)
         self._pool_lists = bool(pool_lists)
-        self._finish_init(nseq, ltot, psets_per_record, interchainonly, ext, mul, max_structs, cand_per_nt, device, fp32, bpp, mul_shared)
+        self._job_lists(nseq, psets_per_record)
+        self._describe(interchainonly, ext, mul, max_structs, cand_per_nt, fp32, bpp, mul_shared)
+        self._create_on_device(device)
 
     def _host_arrays(self, prepared):
-        """The per-position arrays of the batch from a list of Prepared records; (nseq, total positions)."""
+        """The per-position arrays of the batch from a list of Prepared records; the number of records."""
         self.prepared = prepared
         nseq = len(prepared)
         self.seq_off = np.zeros(nseq + 1, np.int32)
@@ -98,11 +101,10 @@ class Batch:
                 self.rbp_off[k + 1] = len(p.rbps)
         np.cumsum(self.rbp_off, out=self.rbp_off)
         self.rbps = np.array(rbps, np.int32).reshape(-1) if rbps else np.zeros(2, np.int32)
-        return nseq, ltot
+        return nseq
 
-    def _finish_init(self, nseq, ltot, psets_per_record, interchainonly, ext, mul, max_structs, cand_per_nt, device, fp32, bpp, mul_shared):
-        torch, L = self.torch, self.L
-        # unique paramsets by identity
+    def _job_lists(self, nseq, psets_per_record):
+        """The batch's jobs, one per (record, paramset of its list), and its unique paramsets (by identity)."""
         uniq, self.psets_py = {}, []
         first = psets_per_record[0] if nseq else []
         if nseq and all(pl is first for pl in psets_per_record):
@@ -134,7 +136,13 @@ class Batch:
             self.job_seq = np.array(job_seq, np.int32)
             self.job_pset = np.array(job_pset, np.int32)
         self.psets_c = (_lib.ParamSet * len(self.psets_py))(*[_pset_struct(p) for p in self.psets_py])
-        njobs = len(self.job_seq)
+        self.njobs = len(self.job_seq)
+        self.nseq = nseq
+
+    def _describe(self, interchainonly=False, ext=None, mul=None, max_structs=0, cand_per_nt=0, fp32=True, bpp=None, mul_shared=None):
+        """Fills self.desc (sq_batch_desc) from the host arrays and the job lists: no device work -- torch is touched only for
+        mul_shared's matrix, which lives on the GPU."""
+        nseq, njobs, ltot = self.nseq, self.njobs, int(self.seq_off[-1])
         d = _lib.BatchDesc()
         d.nseq = nseq
         d.seq_off = _ptr(self.seq_off, C.POINTER(C.c_int32))
@@ -168,6 +176,7 @@ class Batch:
             self._mul = ptr_array(mul)
             d.mul_score = C.cast(self._mul, C.POINTER(C.c_void_p))
         if mul_shared is not None:
+            import torch
             M, cols, maxabs = mul_shared
             assert M.is_cuda and M.dtype == torch.float64 and M.dim() == 2 and M.shape[0] == M.shape[1] and M.is_contiguous()
             self._mul_M = M
@@ -188,28 +197,27 @@ class Batch:
         d.cand_per_nt = int(cand_per_nt)
         d.batch_flags = (0 if fp32 else _lib.BATCH_NO_FP32) | (_lib.BATCH_POOL_LISTS if self._pool_lists else 0)
         self.desc = d
+
+    def workspace_bytes(self):
+        """Bytes of device workspace the described batch needs (sq_batch_workspace_bytes: arithmetic, no device)."""
         nbytes = C.c_size_t(0)
-        _lib.check(L.sq_batch_workspace_bytes(C.byref(d), C.byref(nbytes)))
+        _lib.check(_lib.load().sq_batch_workspace_bytes(C.byref(self.desc), C.byref(nbytes)))
+        return nbytes.value
+
+    def _create_on_device(self, device):
+        """The workspace tensor and the device batch (sq_batch_create) of the described batch."""
+        torch, L = self.torch, self.L
+        nbytes = self.workspace_bytes()
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-        # (sizes in coarse steps: batches of a stream differ by a few records, and torch's caching allocator only hands a cached
-        # block back for a request it nearly fits -- every new size was a hipMalloc, the occasional one with a device-wide
-        # free of cached blocks in front: 40-190 ms steps in the stream leg)
-        # (sixteen size classes per octave from 256 MB on: the 6 GB workspaces of a stream's batches -- 12 SRtest150 sets each --
-        # differ by a few per cent, which in 64 MB steps was a new size every other step: torch's reserved memory grew from 95
-        # to 173 GB over fourteen steps of the pipelined stream, and a step paid hundreds of ms for the device-wide free)
-        want = nbytes.value + 256
-        step = (1 << (want.bit_length() - 5)) if want >= (256 << 20) else (8 << 20) if want >= (16 << 20) else (1 << 20)
-        self.workspace = torch.empty((want + step - 1) // step * step, dtype=torch.uint8, device=self.device)
+        self.workspace = torch.empty(workspace_size_class(nbytes + 256), dtype=torch.uint8, device=self.device)
         base = self.workspace.data_ptr()
         aligned = (base + 255) // 256 * 256
         self.stream = torch.cuda.current_stream(self.device)
         h = C.c_void_p()
-        _lib.check(L.sq_batch_create(C.byref(h), C.byref(d), C.c_void_p(aligned),
-                                     C.c_size_t(nbytes.value), C.c_void_p(self.stream.cuda_stream)))
+        _lib.check(L.sq_batch_create(C.byref(h), C.byref(self.desc), C.c_void_p(aligned),
+                                     C.c_size_t(nbytes), C.c_void_p(self.stream.cuda_stream)))
         self.h = h
         self._refs = None
-        self.njobs = njobs
-        self.nseq = nseq
 
     # -- lifecycle
     def close(self):

@@ -82,11 +82,54 @@ struct Layout {
     size_t off_algo, algo_bytes;     // scratch of the Hungarian / Nussinov kernels (Edmonds borrows the end of the candidate arena)
     int32_t pool_pt;                 // stems per slot (0: no device pools for this batch)
     int64_t chain_T;                 // summed stem capacity of all jobs
+    int32_t chain_tmax;              // most stems a structure of any job can hold (>= 1)
+    std::vector<double> pset_runs;   // per paramset: share of the cells that start a maximal run of >= minlen
     size_t total;
     int64_t ltot, sdf_len, mat32_floats, mat64_doubles, cand_records, bits_words;
     int32_t maxn, stride, max_structs, strand_cap, cpn, fbstride;
     uint32_t out_cap;
 };
+
+// What one job takes from the workspace.  plan() sums these, the job stage of sq_batch_create hands out offsets from the
+// same values: a region is sized and filled from ONE description.
+struct JobNeed {
+    int32_t n, ld;                   // length, row pitch of the fp32 matrix
+    int32_t nw, bpitch;              // diagonal bit matrix: word-rows, words per word-row
+    bool fp32;                       // an n x ld fp32 matrix
+    int32_t has_ext;                 // n x n fp64 matrices (SqJob::has_ext): 1 the caller's score + boolean matrix (two), 2 weights or a bpp term (one), 0 none
+    int32_t mulsh;                   // weighted by the shared matrix through the gap map: no matrix of its own
+    int32_t mat64_diag;              // SQ_MUL_GATHER=1: the gather kernel writes score x weight, diagonal-major (sq_cells.h)
+    int32_t ext_add;                 // has_ext == 2: the term is added (bpp < 0)
+    int32_t tcap;                    // most stems one structure can hold (chain_tcap)
+    int64_t cand_est, cand_cap;      // candidate records per structure: the estimate of the maximal runs; at least cand_per_nt per nucleotide
+    int64_t mat32_floats() const { return fp32 ? (int64_t)align_up((size_t)n * ld, 64) : 0; }
+    int64_t mat64_doubles() const { return (has_ext == 1 ? 2 : has_ext == 2 ? 1 : 0) * (int64_t)n * n; }
+    int64_t bits_words() const { return (int64_t)nw * bpitch; }
+};
+
+// (reads L.sw, L.cpn, L.mul_direct and L.pset_runs, which plan() sets before its job loop; job j's sequence and paramset are in range)
+JobNeed job_need(const sq_batch_desc *d, const Layout &L, int j)
+{
+    JobNeed q;
+    const int s = d->job_seq[j], p = d->job_pset[j];
+    q.n = d->seq_off[s + 1] - d->seq_off[s];
+    q.ld = ld_of(q.n, L.sw); q.nw = bits_nw(q.n); q.bpitch = bits_pitch(q.n);
+    const bool ext = d->ext_score && d->ext_score[j];
+    const bool own = d->mul_score && d->mul_score[j];
+    const bool term = d->bpp_term && d->bpp_term[j];
+    const bool shared = d->mul_shared && d->mul_shared[j];
+    q.mulsh = (shared && !ext && L.mul_direct) ? 1 : 0;
+    q.has_ext = ext ? 1 : (own || term || (shared && !q.mulsh)) ? 2 : 0;
+    q.mat64_diag = (shared && !ext && !q.mulsh) ? 1 : 0;
+    q.ext_add = term && d->psets[p].bpp < 0 ? 1 : 0;
+    // (jobs weighted by the shared stem matrix need no fp32 matrix: their product is formed by the gather kernel)
+    q.fp32 = want_fp32(d) || ext || own || term;
+    q.tcap = chain_tcap(q.n, d->psets[p].minlen);
+    const double est = 0.117 * (double)q.n * q.n * L.pset_runs[p] * 1.6 + 256;   // maximal runs with len >= minlen
+    q.cand_est = (int64_t)est;
+    q.cand_cap = std::max<int64_t>((int64_t)L.cpn * q.n, q.cand_est);
+    return q;
+}
 
 int plan(const sq_batch_desc *d, Layout &L)
 {
@@ -100,22 +143,22 @@ int plan(const sq_batch_desc *d, Layout &L)
     L.cpn = d->cand_per_nt > 0 ? d->cand_per_nt : 32;
     L.mat32_floats = 0; L.mat64_doubles = 0; L.bits_words = 0;
     L.mul_direct = d->mul_matrix_dev != nullptr && !L.sw.mul_gather;
-    int64_t sum_cap = 0;
+    L.pset_runs.resize(d->npset);
+    for (int p = 0; p < d->npset; p++) L.pset_runs[p] = std::pow(0.375, std::max(1.0, std::ceil(d->psets[p].minlen)) - 1.0);
+    // the jobs' needs, summed; chained rounds and pools: per job, room for the most stems a structure can hold (disjoint stems
+    // of >= minlen pairs) -- their sum and their maximum
+    int64_t sum_cap = 0, maxcap = (int64_t)L.cpn * L.maxn + 256;
+    L.chain_T = 0; L.chain_tmax = 1;
     for (int j = 0; j < d->njobs; j++) {
         const int s = d->job_seq[j];
         if (s < 0 || s >= d->nseq || d->job_pset[j] < 0 || d->job_pset[j] >= d->npset) { sq_set_error("bad job"); return -1; }
-        const int64_t n = d->seq_off[s + 1] - d->seq_off[s];
-        const bool ext_any = (d->ext_score && d->ext_score[j]) || (d->mul_score && d->mul_score[j]) ||
-                             (d->bpp_term && d->bpp_term[j]) || (d->mul_shared && d->mul_shared[j]);
-        // (jobs weighted by the shared stem matrix need no fp32 matrix: their product is formed by the gather kernel)
-        const bool shared_only = d->mul_shared && d->mul_shared[j] && !(d->ext_score && d->ext_score[j]);
-        if (want_fp32(d) || (ext_any && !shared_only)) L.mat32_floats += (int64_t)align_up((size_t)(n * ld_of((int)n, L.sw)), 64);
-        L.bits_words += (int64_t)bits_nw((int)n) * bits_pitch((int)n);
-        const bool ext = d->ext_score && d->ext_score[j];
-        const bool mul = (d->mul_score && d->mul_score[j]) || (d->bpp_term && d->bpp_term[j]) ||
-                         (d->mul_shared && d->mul_shared[j] && !L.mul_direct);
-        if (ext) L.mat64_doubles += 2 * n * n;
-        else if (mul) L.mat64_doubles += n * n;
+        const JobNeed need = job_need(d, L, j);
+        L.mat32_floats += need.mat32_floats();
+        L.bits_words += need.bits_words();
+        L.mat64_doubles += need.mat64_doubles();
+        maxcap = std::max<int64_t>(maxcap, need.cand_est);
+        sum_cap += need.cand_cap;
+        L.chain_T += need.tcap; L.chain_tmax = std::max(L.chain_tmax, need.tcap);
     }
     L.mat32_floats += 1024 + (int64_t)160 * ld_of(L.maxn, L.sw);     // reads of rows past a short segment stay inside the arena
     L.sdf_len = 0;
@@ -126,18 +169,6 @@ int plan(const sq_batch_desc *d, Layout &L)
     L.stride = (int32_t)align_up((size_t)L.maxn + 2, 32);
     L.fbstride = 2 * (L.stride / 32 + 8);
     L.strand_cap = (int32_t)std::min<int64_t>((int64_t)L.max_structs * 64 + L.maxn, 1 << 24);
-    int64_t maxcap = (int64_t)L.cpn * L.maxn + 256;
-    {
-        std::vector<double> runs(d->npset);                 // share of the cells that start a maximal run of >= minlen (per paramset)
-        for (int p = 0; p < d->npset; p++) runs[p] = std::pow(0.375, std::max(1.0, std::ceil(d->psets[p].minlen)) - 1.0);
-        for (int j = 0; j < d->njobs; j++) {
-            const int sq = d->job_seq[j];
-            const double nn = d->seq_off[sq + 1] - d->seq_off[sq];
-            const int64_t cj = (int64_t)(0.117 * nn * nn * runs[d->job_pset[j]] * 1.6 + 256);
-            maxcap = std::max<int64_t>(maxcap, cj);
-            sum_cap += std::max<int64_t>(cj, (int64_t)L.cpn * (int64_t)nn);
-        }
-    }
     L.cand_records = std::min<int64_t>((int64_t)L.max_structs * maxcap, (int64_t)160 << 20);   // (5 GiB of 32-byte records at most)
     // ... unless ONE structure per job needs more: the rows of a long alignment (512 x 4,700 nt: 50 MB of run records each) fold
     // as chains of ONE launch when the arena holds them all -- five launches of a fifth of the chip's blocks otherwise (40 GiB at most)
@@ -181,10 +212,7 @@ int plan(const sq_batch_desc *d, Layout &L)
         // short walks it replaces --, 1,024 x 1000 nt one fold alone 4.6 / 4.8 (scoring kernel 2.18 / 2.48), two sub-batches side by
         // side 4.45 / 4.2, 1,000 x 2000 nt 27.0 / 29.6: from 800 nt on)
         const int ctx_min_n = L.sw.ctx_min_n;
-        int pt_max = 1;
-        for (int j = 0; j < d->njobs; j++)
-            pt_max = std::max(pt_max, chain_tcap(d->seq_off[d->job_seq[j] + 1] - d->seq_off[d->job_seq[j]], d->psets[d->job_pset[j]].minlen));
-        const int cap = std::min(1024, 2 * pt_max + 2) + 1;
+        const int cap = std::min(1024, 2 * L.chain_tmax + 2) + 1;
         int lv = 0;
         const size_t per_gap = sq_context_bytes_per_gap(cap, &lv);
         const size_t total = per_gap * (size_t)cap * (size_t)L.max_structs;
@@ -196,18 +224,14 @@ int plan(const sq_batch_desc *d, Layout &L)
             L.off_ctx_ok = take((size_t)L.max_structs);
         }
     }
-    // chained rounds: per job, room for the most stems a structure can hold (disjoint stems of >= minlen pairs)
-    L.chain_T = 0;
-    for (int j = 0; j < d->njobs; j++) L.chain_T += chain_tcap(d->seq_off[d->job_seq[j] + 1] - d->seq_off[d->job_seq[j]], d->psets[d->job_pset[j]].minlen);
+    // chained rounds: per job, room for the most stems a structure can hold (L.chain_T in all)
     L.off_crec = take(sizeof(SqChain) * (size_t)d->njobs);
     L.off_cstems = take(sizeof(SqChainStem) * (size_t)L.chain_T);
     L.off_cstrands = take(sizeof(SqStrand) * 4 * (size_t)L.chain_T);
     L.off_csidx = take(sizeof(int16_t) * 4 * (size_t)L.chain_T);
     L.off_cnfin = take(64);
     // device pools: two generations of max_structs slots, each with room for the most stems any job's structure can hold
-    L.pool_pt = 0;
-    for (int j = 0; j < d->njobs; j++)
-        L.pool_pt = std::max(L.pool_pt, chain_tcap(d->seq_off[d->job_seq[j] + 1] - d->seq_off[d->job_seq[j]], d->psets[d->job_pset[j]].minlen));
+    L.pool_pt = L.chain_tmax;
     // (such batches keep the host-driven loop: lists longer than the level scratch holds; slot offsets beyond 31 bits)
     if (L.pool_pt > SQ_CHAIN_TMAX || 8 * (int64_t)L.max_structs * L.pool_pt >= ((int64_t)1 << 31)) L.pool_pt = 0;
     {
@@ -237,12 +261,9 @@ int plan(const sq_batch_desc *d, Layout &L)
         // the log of final structures: every structure of every pool ends there once -- measured: 1.4 x the largest generation.
         // Two entries per structure slot (65,536 at least, 4 Mi at most) + one per job (chained rounds, E / H / N stemsets),
         // with a third of the most stems a structure can hold each (8 .. 128) + every job's stem capacity once
-        int pt_any = 1;
-        for (int j = 0; j < d->njobs; j++)
-            pt_any = std::max(pt_any, chain_tcap(d->seq_off[d->job_seq[j] + 1] - d->seq_off[d->job_seq[j]], d->psets[d->job_pset[j]].minlen));
         const int64_t want = std::min<int64_t>(std::max<int64_t>(65536, 2 * (int64_t)L.max_structs), (int64_t)4 << 20);
         L.fin_cap = (uint32_t)(want + 2 * (int64_t)d->njobs);
-        L.fin_stem_cap = (uint32_t)std::min<int64_t>(std::min<int64_t>(want * std::min(std::max(pt_any / 3, 8), 128), (int64_t)48 << 20) + 2 * L.chain_T,
+        L.fin_stem_cap = (uint32_t)std::min<int64_t>(std::min<int64_t>(want * std::min(std::max(L.chain_tmax / 3, 8), 128), (int64_t)48 << 20) + 2 * L.chain_T,
                                                      (int64_t)0x7FFFFFF0);
         if (L.sw.fin_stem_cap) L.fin_stem_cap = (uint32_t)std::min<int64_t>(L.fin_stem_cap, L.sw.fin_stem_cap);   // (tests: the log's stem room runs out)
         L.pow_len = 4 * L.maxn + 16;
@@ -287,18 +308,92 @@ extern "C" int sq_batch_workspace_bytes(const sq_batch_desc *desc, size_t *bytes
     return 0;
 }
 
-extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws, size_t ws_bytes, void *hip_stream)
-{
+namespace {
+// Uploads go through a pinned staging buffer of the library.  A copy straight from pageable memory makes the runtime
+// register the caller's pages with the driver; when the allocator later returns such pages to the kernel (munmap /
+// heap trim) the driver evicts the process's queues for tens of milliseconds -- measured as 20-35 ms stalls in the
+// third fold after a batch was created.  Buffers larger than the staging area go in slices.
+struct Stager {
+    hipStream_t st = nullptr; char *buf = nullptr; size_t cap = 0, cur = 0;
+    int rc = 0;                      // the first failure: every later put() returns it and uploads nothing
+    ~Stager() { if (buf) { hipStreamSynchronize(st); sq_pinned_put(buf); } }
+    int put(const void *dst, const void *src, size_t bytes)       // (const: the device context holds its inputs as pointers to const)
+    {
+        const char *s = (const char *)src; char *d = (char *)dst;
+        while (bytes && !rc) {
+            if (cur == cap) { rc = sq_check(hipStreamSynchronize(st), "upload"); if (rc) return rc; cur = 0; }
+            const size_t take = std::min(bytes, cap - cur);
+            memcpy(buf + cur, s, take);
+            rc = sq_check(hipMemcpyAsync(d, buf + cur, take, hipMemcpyHostToDevice, st), "upload");
+            if (rc) return rc;
+            cur += (take + 255) & ~(size_t)255; if (cur > cap) cur = cap;
+            s += take; d += take; bytes -= take;
+        }
+        return rc;
+    }
+};
+
+// phase timers of sq_batch_create: SQ_DEFS=-DSQ_CREATE_PROF python -m squarna_amd.build; one line per call on stderr
 #ifdef SQ_CREATE_PROF
-    // (phase timers of this function: SQ_DEFS=-DSQ_CREATE_PROF python -m squarna_amd.build; one line per call on stderr)
-    std::vector<std::pair<const char *, double>> _cp; _cp.emplace_back("start", now_s());
+struct CreateProf {
+    std::vector<std::pair<const char *, double>> t{{"start", now_s()}};
+    void mark(const char *what) { t.emplace_back(what, now_s()); }
+    void report() const
+    {
+        std::string line = "[sq_batch_create ms]";
+        for (size_t k = 1; k < t.size(); k++) { char s[64]; snprintf(s, sizeof s, " %s %.2f", t[k].first, (t[k].second - t[k - 1].second) * 1e3); line += s; }
+        fprintf(stderr, "%s\n", line.c_str());
+    }
+};
+#else
+struct CreateProf { void mark(const char *) {} void report() const {} };
 #endif
+
+// The batch until sq_batch_create hands it out: any return before release() deletes it, after the stream has run dry when
+// something was enqueued on it (uploads in flight read the library's staging buffer, kernels write the workspace).
+struct BatchOwner {
+    sq_batch *b = nullptr; bool enqueued = false;
+    ~BatchOwner() { if (!b) return; if (enqueued) hipStreamSynchronize(b->stream); delete b; }
+    sq_batch *release() { sq_batch *r = b; b = nullptr; return r; }
+};
+
+template <class T> inline T *at(char *base, size_t off) { return reinterpret_cast<T *>(base + off); }
+
+// One sq_batch_create: the stages in the order they run, and the host arrays that more than one of them needs.
+struct BatchCreate {
+    const sq_batch_desc *d;
     Layout L;
-    int r = plan(d, L);
-    if (r) return r;
-#ifdef SQ_CREATE_PROF
-    _cp.emplace_back("plan", now_s());
-#endif
+    BatchOwner own;                  // (declared before `up`: the staging buffer is idle and back in the cache before the batch goes)
+    sq_batch *b = nullptr;           // own.b
+    char *base = nullptr;            // the workspace
+    std::vector<uint8_t> inc4, e0, ridx, seq_def;      // per position: minimal span, restraint-pair ends, reactivity level; per sequence: every reactivity 0.5 (:273)
+    std::vector<int16_t> chain;
+    std::vector<SqPsetDev> pd;
+    std::vector<double> sdf, powtab, rftab;
+    std::vector<int32_t> seq_levels, seq_rf;
+    std::vector<uint32_t> rbpk;
+    int64_t m32 = 0, m64 = 0, mbits = 0;               // handed out to the jobs: fp32 floats, fp64 doubles, bit words
+    Stager up;
+    CreateProf prof;
+
+    int check_request(const void *ws, size_t ws_bytes) const;
+    void host_copies(void *hip_stream);
+    int position_arrays();
+    void paramset_records();
+    void reactivity_levels();
+    void job_records();
+    int check_against_plan() const;
+    void carve();
+    int open_uploads();
+    int upload_inputs();
+    int upload_tail_tables();
+    int upload_caller_matrices();
+    int upload_shared_matrix();
+    int pinned_buffers();
+};
+
+int BatchCreate::check_request(const void *ws, size_t ws_bytes) const
+{
     if (!ws || ws_bytes < L.total) { sq_set_error("workspace too small"); return -2; }
     if (((uintptr_t)ws & 255) != 0) { sq_set_error("workspace must be 256-byte aligned"); return -2; }
     for (int j = 0; j < d->njobs; j++) {
@@ -317,7 +412,11 @@ extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws,
             sq_set_error("a job takes either bpp_term or mul_score / caller matrices, not both"); return -4;
         }
     }
-    sq_batch *b = new sq_batch();
+    return 0;
+}
+
+void BatchCreate::host_copies(void *hip_stream)
+{
     b->bsw = L.sw;
     sq_read_fold_switches(b->sw);                           // (every sq_fold refreshes them; the per-call ops read these)
     b->stream = (hipStream_t)hip_stream;
@@ -342,15 +441,14 @@ extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws,
     b->cand_records = L.cand_records; b->out_cap = L.out_cap; b->strand_cap = L.strand_cap;
     b->mat32_bytes = 4 * (size_t)L.mat32_floats;
     b->has_fp32 = want_fp32(d);
+}
 
-#ifdef SQ_CREATE_PROF
-    _cp.emplace_back("copies", now_s());
-#endif
-    char *base = (char *)ws;
-    // ---- per-position derived arrays (host, O(N)) ----
-    std::vector<uint8_t> inc4(L.ltot);
-    std::vector<int16_t> chain(L.ltot, 0);
-    std::vector<uint8_t> e0(L.ltot, 0);
+// ---- per-position derived arrays (host, O(N)) ----
+int BatchCreate::position_arrays()
+{
+    inc4.assign(L.ltot, 0);
+    chain.assign(L.ltot, 0);
+    e0.assign(L.ltot, 0);
     {
         uint32_t seen = 0;
         for (uint8_t cd : b->codes) if (cd < 29) seen |= 1u << cd;
@@ -381,17 +479,18 @@ extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws,
         }
         for (int k = d->rbp_off[s]; k < d->rbp_off[s + 1]; k++) {
             const int v = d->rbps[2 * k], w = d->rbps[2 * k + 1];
-            if (v < 0 || w >= n || v >= w) { delete b; sq_set_error("bad restraint pair"); return -1; }
-            if (e0[off + v] || e0[off + w]) { delete b; sq_set_error("a position in two restraint base pairs"); return -1; }
+            if (v < 0 || w >= n || v >= w) { sq_set_error("bad restraint pair"); return -1; }
+            if (e0[off + v] || e0[off + w]) { sq_set_error("a position in two restraint base pairs"); return -1; }
             e0[off + v] = 1; e0[off + w] = 1;                  // 1: end of a restraint pair (0: free, 255: masked by the structure)
         }
     }
-#ifdef SQ_CREATE_PROF
-    _cp.emplace_back("positions", now_s());
-#endif
-    // ---- paramsets with host-libm pow tables ----
-    std::vector<SqPsetDev> pd(d->npset);
-    std::vector<double> sdf, powtab;
+    return 0;
+}
+
+// ---- paramsets with host-libm pow tables ----
+void BatchCreate::paramset_records()
+{
+    pd.resize(d->npset);
     for (int p = 0; p < d->npset; p++) {
         const sq_paramset &ps = d->psets[p];
         SqPsetDev &x = pd[p];
@@ -456,12 +555,15 @@ extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws,
             for (int k = 0; k < x.sdf_len; k++) sdf.push_back(pow(1.0 / (1.0 + (double)k), ps.distcoef));   // :726
         }
     }
-    // reactivity levels: encoded reactivities (3 / 10 / 26 symbols) take few distinct values per sequence; with <= 16
-    // of them the reactfactor of a cell is a table lookup instead of an fp64 sqrt (and division) per cell and round
-    std::vector<uint8_t> ridx(L.ltot, 0);
-    std::vector<int32_t> seq_levels(d->nseq, 0), seq_rf(d->nseq, -1);
-    std::vector<double> rftab;
-    std::vector<uint8_t> seq_def(d->nseq, 0);                // every reactivity of the sequence 0.5 (:273)
+}
+
+// reactivity levels: encoded reactivities (3 / 10 / 26 symbols) take few distinct values per sequence; with <= 16
+// of them the reactfactor of a cell is a table lookup instead of an fp64 sqrt (and division) per cell and round
+void BatchCreate::reactivity_levels()
+{
+    ridx.assign(L.ltot, 0);
+    seq_levels.assign(d->nseq, 0); seq_rf.assign(d->nseq, -1);
+    seq_def.assign(d->nseq, 0);
     for (int s = 0; s < d->nseq; s++) {
         const int off = d->seq_off[s], n = d->seq_off[s + 1] - off;
         if (!d->reacts || all_half(d->reacts + off, n)) {    // one level (index 0 everywhere: ridx is zeroed), no factor table
@@ -488,13 +590,13 @@ extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws,
                 for (int c2 = 0; c2 < nv; c2++) T[a * 16 + c2] = pow((1.0 - (vals[a] + vals[c2]) / 2.0) * 2.0, 0.5);
         }
     }
-#ifdef SQ_CREATE_PROF
-    _cp.emplace_back("paramsets", now_s());
-#endif
-    // ---- jobs ----
+}
+
+// ---- jobs ----
+void BatchCreate::job_records()
+{
     b->jobs.resize(d->njobs);
-    int64_t m32 = 0, m64 = 0, mbits = 0;
-    std::vector<uint32_t> rbpk((size_t)d->rbp_off[d->nseq]);
+    rbpk.resize((size_t)d->rbp_off[d->nseq]);
     for (size_t k = 0; k < rbpk.size(); k++) rbpk[k] = (uint32_t)d->rbps[2 * k] | ((uint32_t)d->rbps[2 * k + 1] << 16);
     for (int sq = 0; sq < d->nseq; sq++)                       // per sequence by (i + j, i): a diagonal's pairs are one run (sq_scan6_kernel)
         std::sort(rbpk.begin() + d->rbp_off[sq], rbpk.begin() + d->rbp_off[sq + 1], [](uint32_t x, uint32_t y) {
@@ -502,10 +604,8 @@ extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws,
             return sx != sy ? sx < sy : (x & 0xFFFFu) < (y & 0xFFFFu);
         });
     std::vector<double> pset_maxabs(2 * (size_t)d->npset, 0.0);   // largest |cell| a paramset can produce: plain / with reactivity factors
-    std::vector<double> pset_runs(d->npset);                      // share of the cells that start a maximal run of >= minlen
     for (int p = 0; p < d->npset; p++) {
         const sq_paramset &ps = d->psets[p];
-        pset_runs[p] = std::pow(0.375, std::max(1.0, std::ceil(ps.minlen)) - 1.0);
         for (int q = 0; q < 32 * 32; q++) {
             if (!ps.inbps[q]) continue;
             const double w = ps.bpweight[q];
@@ -529,41 +629,35 @@ extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws,
     std::vector<int64_t> shared_bits((size_t)d->nseq * (size_t)std::max(d->npset, 1), -1);
     for (int j = 0; j < d->njobs; j++) {
         SqJob &J = b->jobs[j];
+        const JobNeed need = job_need(d, L, j);
         const int s = d->job_seq[j];
-        J.n = d->seq_off[s + 1] - d->seq_off[s];
-        J.ld = ld_of(J.n, b->bsw); J.seq = s; J.pset = d->job_pset[j];
+        J.n = need.n;
+        J.ld = need.ld; J.seq = s; J.pset = d->job_pset[j];
         J.pos_off = d->seq_off[s];
-        J.mat64_off = -1; J.has_ext = 0;
-        J.nw = bits_nw(J.n); J.bpitch = bits_pitch(J.n);
+        J.nw = need.nw; J.bpitch = need.bpitch;
         J.rb_off = d->rbp_off[s]; J.nrb = d->rbp_off[s + 1] - d->rbp_off[s];
-        const bool ext = d->ext_score && d->ext_score[j];
+        const bool ext = need.has_ext == 1, mul = need.has_ext == 2;
         {
             int64_t &slot = shared_bits[(size_t)s * (size_t)d->npset + (size_t)pset_sig[d->job_pset[j]]];
             if (!ext && !no_share && slot >= 0) { J.bits_off = slot; J.bits_owner = 0; }      // (a caller's boolean matrix: the job's own)
             else {
-                J.bits_off = mbits; J.bits_owner = 1; mbits += (int64_t)J.nw * J.bpitch;
+                J.bits_off = mbits; J.bits_owner = 1; mbits += need.bits_words();
                 if (!ext && !no_share) slot = J.bits_off;
             }
         }
         const bool term = d->bpp_term && d->bpp_term[j];
         const bool shared = d->mul_shared && d->mul_shared[j];
-        J.mulsh = (shared && !ext && L.mul_direct) ? 1 : 0;
-        const bool mul = (d->mul_score && d->mul_score[j]) || term || (shared && !J.mulsh);
-        J.ext_add = term && d->psets[J.pset].bpp < 0 ? 1 : 0;
-        if (ext) { J.mat64_off = m64; J.has_ext = 1; m64 += 2 * (int64_t)J.n * J.n; }
-        else if (mul) { J.mat64_off = m64; J.has_ext = 2; m64 += (int64_t)J.n * J.n; }
+        J.has_ext = need.has_ext; J.mulsh = need.mulsh; J.mat64_diag = need.mat64_diag; J.ext_add = need.ext_add;
+        J.mat64_off = -1;
+        if (need.has_ext) { J.mat64_off = m64; m64 += need.mat64_doubles(); }
         J.mat_off = -1;
-        J.mat64_diag = (shared && !ext && !J.mulsh) ? 1 : 0;   // SQ_MUL_GATHER=1: the gather kernel writes score x weight, diagonal-major (sq_cells.h)
-        if (b->has_fp32 || (J.has_ext && !J.mat64_diag)) { J.mat_off = m32; m32 += (int64_t)align_up((size_t)J.n * J.ld, 64); }
+        if (need.fp32) { J.mat_off = m32; m32 += need.mat32_floats(); }
         const bool def = seq_def[s] != 0;                 // SQRNdbnseq.py:273
         J.default_reacts = def ? 1 : 0;
         J.react_levels = def ? 0 : seq_levels[s];
         J.rf_idx = def ? -1 : seq_rf[s];
         J.interchainonly = d->interchainonly;
-        {
-            const double est = 0.117 * (double)J.n * J.n * pset_runs[J.pset] * 1.6 + 256;   // maximal runs with len >= minlen
-            J.cand_cap = (int32_t)std::max<int64_t>((int64_t)L.cpn * J.n, (int64_t)est);
-        }
+        J.cand_cap = (int32_t)need.cand_cap;
         // bound of |cell| for the scan's fp32 prefilter margin
         double mx = 0;
         const size_t nn = (size_t)J.n * J.n;
@@ -590,235 +684,275 @@ extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws,
         const int KR = K * R;
         b->cell_entries = std::max(b->cell_entries, KR * (KR | 1));
     }
-#ifdef SQ_CREATE_PROF
-    _cp.emplace_back("jobs", now_s());
-#endif
-    // ---- device carve + uploads ----
-    b->ctx.codes = (uint8_t *)(base + L.off_codes); b->ctx.flags = (uint8_t *)(base + L.off_flags);
-    b->ctx.inc4 = (uint8_t *)(base + L.off_inc4); b->ctx.chain = (int16_t *)(base + L.off_chain);
-    b->ctx.e0c = (uint8_t *)(base + L.off_e0); b->ctx.reacts = (double *)(base + L.off_reacts); b->ctx.ridx = (uint8_t *)(base + L.off_ridx);
-    b->ctx.jobs = (SqJob *)(base + L.off_jobs); b->ctx.psets = (SqPsetDev *)(base + L.off_psets);
-    b->ctx.sdftab = (double *)(base + L.off_sdf); b->ctx.rftab = (double *)(base + L.off_rftab);
-    b->ctx.powtab = (double *)(base + L.off_powtab);
-    b->ctx.mat32 = (float *)(base + L.off_mat32); b->ctx.mat64 = (double *)(base + L.off_mat64);
-    b->d_structs = (SqStruct *)(base + L.off_structs); b->d_strands = (SqStrand *)(base + L.off_strands);
-    int16_t *stbase = (int16_t *)(base + L.off_state);
+}
+
+// What the stages above handed out against what plan() booked.  Both read one description (job_need, pow17_entries,
+// all_half), so this cannot fire on any input unless the two halves of this file disagree -- and then the job or table
+// beyond the booked room would overwrite the next region of the workspace without any other sign.
+int BatchCreate::check_against_plan() const
+{
+    if (m32 <= L.mat32_floats && m64 <= L.mat64_doubles && mbits <= L.bits_words &&
+        (int64_t)(rftab.size() / 256) <= L.n_rftab && (int64_t)powtab.size() <= L.pow_entries) return 0;
+    char msg[256];
+    snprintf(msg, sizeof msg, "workspace layout: handed out %lld fp32 / %lld fp64 / %lld bit words, %lld rf tables, %lld pow entries; "
+             "planned %lld / %lld / %lld, %lld, %lld", (long long)m32, (long long)m64, (long long)mbits, (long long)(rftab.size() / 256),
+             (long long)powtab.size(), (long long)L.mat32_floats, (long long)L.mat64_doubles, (long long)L.bits_words,
+             (long long)L.n_rftab, (long long)L.pow_entries);
+    sq_set_error(msg);
+    return -1;
+}
+
+// ---- device carve ----
+void BatchCreate::carve()
+{
+    b->ctx.codes = at<uint8_t>(base, L.off_codes); b->ctx.flags = at<uint8_t>(base, L.off_flags);
+    b->ctx.inc4 = at<uint8_t>(base, L.off_inc4); b->ctx.chain = at<int16_t>(base, L.off_chain);
+    b->ctx.e0c = at<uint8_t>(base, L.off_e0); b->ctx.reacts = at<double>(base, L.off_reacts); b->ctx.ridx = at<uint8_t>(base, L.off_ridx);
+    b->ctx.jobs = at<SqJob>(base, L.off_jobs); b->ctx.psets = at<SqPsetDev>(base, L.off_psets);
+    b->ctx.sdftab = at<double>(base, L.off_sdf); b->ctx.rftab = at<double>(base, L.off_rftab);
+    b->ctx.powtab = at<double>(base, L.off_powtab);
+    b->ctx.mat32 = at<float>(base, L.off_mat32); b->ctx.mat64 = at<double>(base, L.off_mat64);
+    b->d_structs = at<SqStruct>(base, L.off_structs); b->d_strands = at<SqStrand>(base, L.off_strands);
+    int16_t *stbase = at<int16_t>(base, L.off_state);
     const size_t plane = (size_t)L.stride * L.max_structs;
     b->state.P = stbase; b->state.E8 = (uint8_t *)(stbase + plane); b->state.U = stbase + 2 * plane; b->state.SU = stbase + 3 * plane;
     b->state.stride = L.stride;
-    b->state.FB = (uint32_t *)(base + L.off_fb); b->state.fbstride = L.fbstride;
+    b->state.FB = at<uint32_t>(base, L.off_fb); b->state.fbstride = L.fbstride;
     b->ctxtab = SqCtxTab{};
     if (L.ctx_cap) {
-        b->ctxtab.rec = (SqCtxRec *)(base + L.off_ctx_rec); b->ctxtab.depth = (int16_t *)(base + L.off_ctx_depth);
-        b->ctxtab.rmq = (uint16_t *)(base + L.off_ctx_rmq); b->ctxtab.ok = (uint8_t *)(base + L.off_ctx_ok);
+        b->ctxtab.rec = at<SqCtxRec>(base, L.off_ctx_rec); b->ctxtab.depth = at<int16_t>(base, L.off_ctx_depth);
+        b->ctxtab.rmq = at<uint16_t>(base, L.off_ctx_rmq); b->ctxtab.ok = at<uint8_t>(base, L.off_ctx_ok);
         b->ctxtab.cap = L.ctx_cap; b->ctxtab.levels = L.ctx_levels;
     }
-    b->ctx.bits = (uint32_t *)(base + L.off_bits); b->ctx.rbpk = (uint32_t *)(base + L.off_rbpk);
-    b->scan.cand_cnt = (uint32_t *)(base + L.off_cnt); b->scan.ctr = (SqCounters *)(base + L.off_ctr);
-    b->scan.best = (unsigned long long *)(base + L.off_cnt + 4 * align_up((size_t)L.max_structs, 2));
-    b->scan.ok_cnt = (uint32_t *)(base + L.off_cnt + 12 * align_up((size_t)L.max_structs, 2));
-    b->scan.cands = (SqCand *)(base + L.off_cands);
-    b->d_out = (SqOut *)(base + L.off_out);
-    b->chain.chain = (SqChain *)(base + L.off_crec); b->chain.stems = (SqChainStem *)(base + L.off_cstems);
-    b->chain.strands = (SqStrand *)(base + L.off_cstrands); b->chain.sidx = (int16_t *)(base + L.off_csidx);
-    b->chain.d_nfin = (uint32_t *)(base + L.off_cnfin);
+    b->ctx.bits = at<uint32_t>(base, L.off_bits); b->ctx.rbpk = at<uint32_t>(base, L.off_rbpk);
+    b->scan.cand_cnt = at<uint32_t>(base, L.off_cnt); b->scan.ctr = at<SqCounters>(base, L.off_ctr);
+    b->scan.best = at<unsigned long long>(base, L.off_cnt + 4 * align_up((size_t)L.max_structs, 2));
+    b->scan.ok_cnt = at<uint32_t>(base, L.off_cnt + 12 * align_up((size_t)L.max_structs, 2));
+    b->scan.cands = at<SqCand>(base, L.off_cands);
+    b->d_out = at<SqOut>(base, L.off_out);
+    b->chain.chain = at<SqChain>(base, L.off_crec); b->chain.stems = at<SqChainStem>(base, L.off_cstems);
+    b->chain.strands = at<SqStrand>(base, L.off_cstrands); b->chain.sidx = at<int16_t>(base, L.off_csidx);
+    b->chain.d_nfin = at<uint32_t>(base, L.off_cnfin);
     b->chain_T = L.chain_T;
     {   // the device log of final structures and the device tail's arrays
-        b->d_fin = (SqPoolFin *)(base + L.off_fin); b->d_fin_stems = (SqPoolStem *)(base + L.off_fin_stems);
-        b->d_fin_ctr = (uint32_t *)(base + L.off_fin_ctr); b->d_job_evals = (long long *)(base + L.off_jobevals);
+        b->d_fin = at<SqPoolFin>(base, L.off_fin); b->d_fin_stems = at<SqPoolStem>(base, L.off_fin_stems);
+        b->d_fin_ctr = at<uint32_t>(base, L.off_fin_ctr); b->d_job_evals = at<long long>(base, L.off_jobevals);
         b->fin_cap = L.fin_cap; b->fin_stem_cap = L.fin_stem_cap;
-        b->d_refp = (int16_t *)(base + L.off_t_refp); b->d_refn = (int32_t *)(base + L.off_t_refn);
+        b->d_refp = at<int16_t>(base, L.off_t_refp); b->d_refn = at<int32_t>(base, L.off_t_refn);
         b->chain.fin = b->d_fin; b->chain.fin_ctr = b->d_fin_ctr; b->chain.fin_cap = L.fin_cap; b->chain.job_evals = b->d_job_evals;
         SqTailIO &T = b->tail;
         T.fin = b->d_fin; T.fin_stems = b->d_fin_stems; T.nfin_ptr = b->d_fin_ctr; T.chain_stems = b->chain.stems;
         T.fin_cap = L.fin_cap; T.fin_stem_cap = L.fin_stem_cap;
-        uint32_t *tj = (uint32_t *)(base + L.off_t_jobs);
+        uint32_t *tj = at<uint32_t>(base, L.off_t_jobs);
         T.job_cnt = tj; T.job_start = tj + (d->njobs + 1); T.job_fill = tj + 2 * ((size_t)d->njobs + 1);
         T.job_evals = b->d_job_evals; T.njobs = d->njobs; T.nseq = d->nseq;
-        T.seq_job0 = (int32_t *)(base + L.off_t_seqjob0);
-        T.ord = (uint32_t *)(base + L.off_t_ord); T.ord2 = T.ord + L.fin_cap;
-        T.cstems = (SqPoolStem *)(base + L.off_t_cstems); T.cs_n = (uint32_t *)(base + L.off_t_csn);
-        T.hash = (unsigned long long *)(base + L.off_t_hash); T.rep = (uint32_t *)(base + L.off_t_rep);
-        T.mask = (unsigned long long *)(base + L.off_t_mask); T.scores = (double *)(base + L.off_t_scores);
-        T.dlist = (uint32_t *)(base + L.off_t_dlist); T.rlist = (uint32_t *)(base + L.off_t_rlist);
-        T.seqs = (SqTailSeq *)(base + L.off_t_seqs);
-        T.pow17h = (double *)(base + L.off_t_pow); T.pow17h_len = L.pow_len;
+        T.seq_job0 = at<int32_t>(base, L.off_t_seqjob0);
+        T.ord = at<uint32_t>(base, L.off_t_ord); T.ord2 = T.ord + L.fin_cap;
+        T.cstems = at<SqPoolStem>(base, L.off_t_cstems); T.cs_n = at<uint32_t>(base, L.off_t_csn);
+        T.hash = at<unsigned long long>(base, L.off_t_hash); T.rep = at<uint32_t>(base, L.off_t_rep);
+        T.mask = at<unsigned long long>(base, L.off_t_mask); T.scores = at<double>(base, L.off_t_scores);
+        T.dlist = at<uint32_t>(base, L.off_t_dlist); T.rlist = at<uint32_t>(base, L.off_t_rlist);
+        T.seqs = at<SqTailSeq>(base, L.off_t_seqs);
+        T.pow17h = at<double>(base, L.off_t_pow); T.pow17h_len = L.pow_len;
         T.fallback = b->d_fin_ctr + 3;
     }
-    b->chain_tmax = 1;
-    for (int j = 0; j < d->njobs; j++)
-        b->chain_tmax = std::max(b->chain_tmax, chain_tcap(d->seq_off[d->job_seq[j] + 1] - d->seq_off[d->job_seq[j]], d->psets[d->job_pset[j]].minlen));
+    b->chain_tmax = L.chain_tmax;
     b->algo_scratch = L.algo_bytes ? base + L.off_algo : nullptr; b->algo_bytes = L.algo_bytes; b->algo_used = 0;
     if (L.pool_pt) {
         SqPoolIO &P = b->pool_io;
-        P.structs = (SqStruct *)(base + L.off_pstructs); P.recs = (SqChain *)(base + L.off_precs);
-        P.stems = (SqChainStem *)(base + L.off_pstems); P.strands = (SqStrand *)(base + L.off_pstrands);
-        P.sidx = (int16_t *)(base + L.off_psidx);
+        P.structs = at<SqStruct>(base, L.off_pstructs); P.recs = at<SqChain>(base, L.off_precs);
+        P.stems = at<SqChainStem>(base, L.off_pstems); P.strands = at<SqStrand>(base, L.off_pstrands);
+        P.sidx = at<int16_t>(base, L.off_psidx);
         P.smax = L.max_structs; P.pt = L.pool_pt; P.cmax = 64;
-        P.jobs = (SqPoolJob *)(base + L.off_pjobs); P.jobrec_of = (int32_t *)(base + L.off_pjobrec);
-        P.nchild = (int32_t *)(base + L.off_pnchild); P.child_off = (int32_t *)(base + L.off_pchoff);
-        P.finalflag = (uint8_t *)(base + L.off_pflag); P.chosen = (SqPoolPick *)(base + L.off_pchosen); P.parent_of = (int32_t *)(base + L.off_pparent);
-        P.hdr = (SqPoolHdr *)(base + L.off_phdr);
+        P.jobs = at<SqPoolJob>(base, L.off_pjobs); P.jobrec_of = at<int32_t>(base, L.off_pjobrec);
+        P.nchild = at<int32_t>(base, L.off_pnchild); P.child_off = at<int32_t>(base, L.off_pchoff);
+        P.finalflag = at<uint8_t>(base, L.off_pflag); P.chosen = at<SqPoolPick>(base, L.off_pchosen); P.parent_of = at<int32_t>(base, L.off_pparent);
+        P.hdr = at<SqPoolHdr>(base, L.off_phdr);
         P.fin = b->d_fin; P.fin_stems = b->d_fin_stems; P.fin_cap = L.fin_cap; P.fin_stem_cap = L.fin_stem_cap;
         P.fin_ctr = b->d_fin_ctr; P.job_evals = b->d_job_evals;
         P.kept_ctr = nullptr;
         b->kept = SqKept{nullptr, nullptr, nullptr, nullptr, 0u, 0};
-        if (L.kept_pages) b->kept = SqKept{base + L.off_kpages, (uint32_t *)(base + L.off_kctr), (uint32_t *)(base + L.off_kcnt), (uint32_t *)(base + L.off_ktab), L.kept_pages, 1};
+        if (L.kept_pages) b->kept = SqKept{base + L.off_kpages, at<uint32_t>(base, L.off_kctr), at<uint32_t>(base, L.off_kcnt), at<uint32_t>(base, L.off_ktab), L.kept_pages, 1};
     }
+}
 
+// ---- uploads ----
+int BatchCreate::open_uploads()
+{
+    up.st = b->stream;
+    own.enqueued = true;
+    size_t want = (size_t)L.ltot * 16 + 8 * rftab.size() + 8 * powtab.size() + 8 * (size_t)L.pow_len + 4 * ((size_t)d->nseq + 1) + sizeof(SqJob) * d->njobs + sizeof(SqPsetDev) * d->npset + 8 * sdf.size() + 4 * rbpk.size() + 16384;
+    for (int j = 0; j < d->njobs; j++)
+        if (b->jobs[j].has_ext && !(d->mul_shared && d->mul_shared[j])) want += (size_t)b->jobs[j].n * b->jobs[j].n * 8 * (b->jobs[j].has_ext == 1 ? 2 : 1);
+    up.cap = std::min<size_t>(std::max<size_t>(want, (size_t)1 << 20), (size_t)64 << 20) & ~(size_t)255;
+    void *pb = nullptr;
+    if (sq_pinned_get(&pb, up.cap)) return 2;
+    up.buf = (char *)pb;
+    return 0;
+}
+
+int BatchCreate::upload_inputs()
+{
     hipStream_t st = b->stream;
-    // Uploads go through a pinned staging buffer of the library.  A copy straight from pageable memory makes the runtime
-    // register the caller's pages with the driver; when the allocator later returns such pages to the kernel (munmap /
-    // heap trim) the driver evicts the process's queues for tens of milliseconds -- measured as 20-35 ms stalls in the
-    // third fold after a batch was created.  Buffers larger than the staging area go in slices.
-    struct Stager {
-        hipStream_t st; char *buf = nullptr; size_t cap = 0, cur = 0; int rc = 0;
-        ~Stager() { if (buf) { hipStreamSynchronize(st); sq_pinned_put(buf); } }
-        int put(void *dst, const void *src, size_t bytes)
-        {
-            const char *s = (const char *)src; char *d = (char *)dst;
-            while (bytes) {
-                if (cur == cap) { rc = sq_check(hipStreamSynchronize(st), "upload"); if (rc) return rc; cur = 0; }
-                const size_t take = std::min(bytes, cap - cur);
-                memcpy(buf + cur, s, take);
-                rc = sq_check(hipMemcpyAsync(d, buf + cur, take, hipMemcpyHostToDevice, st), "upload");
-                if (rc) return rc;
-                cur += (take + 255) & ~(size_t)255; if (cur > cap) cur = cap;
-                s += take; d += take; bytes -= take;
-            }
-            return 0;
-        }
-    } stager;
-    stager.st = st;
-    {
-        size_t want = (size_t)L.ltot * 16 + 8 * rftab.size() + 8 * powtab.size() + 8 * (size_t)L.pow_len + 4 * ((size_t)d->nseq + 1) + sizeof(SqJob) * d->njobs + sizeof(SqPsetDev) * d->npset + 8 * sdf.size() + 4 * rbpk.size() + 16384;
-        for (int j = 0; j < d->njobs; j++)
-            if (b->jobs[j].has_ext && !(d->mul_shared && d->mul_shared[j])) want += (size_t)b->jobs[j].n * b->jobs[j].n * 8 * (b->jobs[j].has_ext == 1 ? 2 : 1);
-        stager.cap = std::min<size_t>(std::max<size_t>(want, (size_t)1 << 20), (size_t)64 << 20) & ~(size_t)255;
-        void *pb = nullptr;
-        if (sq_pinned_get(&pb, stager.cap)) { delete b; return 2; }
-        stager.buf = (char *)pb;
-    }
-#define UP(dst, src, bytes) do { int _r = stager.put((void *)(dst), (src), (bytes)); if (_r) { hipStreamSynchronize(st); delete b; return _r; } } while (0)
-#ifdef SQ_CREATE_PROF
-    _cp.emplace_back("carve", now_s());
-#endif
-    UP(b->ctx.codes, b->codes.data(), L.ltot); UP(b->ctx.flags, b->flags.data(), L.ltot);
-    UP(b->ctx.inc4, inc4.data(), L.ltot); UP(b->ctx.chain, chain.data(), L.ltot * 2);
-    UP(b->ctx.e0c, e0.data(), L.ltot);
-    if (d->reacts) UP(b->ctx.reacts, b->reacts.data(), L.ltot * 8);
+    up.put(b->ctx.codes, b->codes.data(), L.ltot); up.put(b->ctx.flags, b->flags.data(), L.ltot);
+    up.put(b->ctx.inc4, inc4.data(), L.ltot); up.put(b->ctx.chain, chain.data(), L.ltot * 2);
+    up.put(b->ctx.e0c, e0.data(), L.ltot);
+    if (d->reacts) up.put(b->ctx.reacts, b->reacts.data(), L.ltot * 8);
     else hipLaunchKernelGGL(sq_fill_f64_kernel, dim3(256), dim3(256), 0, st, const_cast<double *>(b->ctx.reacts), (long long)L.ltot, 0.5);
-    UP(b->ctx.ridx, ridx.data(), L.ltot);
+    up.put(b->ctx.ridx, ridx.data(), L.ltot);
     b->ridx = ridx;
-    UP(b->ctx.jobs, b->jobs.data(), sizeof(SqJob) * d->njobs);
-    UP(b->ctx.psets, pd.data(), sizeof(SqPsetDev) * d->npset);
-    if (!sdf.empty()) UP(b->ctx.sdftab, sdf.data(), 8 * sdf.size());
-    if (!rftab.empty()) UP(b->ctx.rftab, rftab.data(), 8 * rftab.size());
-    if (!powtab.empty()) UP(b->ctx.powtab, powtab.data(), 8 * powtab.size());
+    up.put(b->ctx.jobs, b->jobs.data(), sizeof(SqJob) * d->njobs);
+    up.put(b->ctx.psets, pd.data(), sizeof(SqPsetDev) * d->npset);
+    if (!sdf.empty()) up.put(b->ctx.sdftab, sdf.data(), 8 * sdf.size());
+    if (!rftab.empty()) up.put(b->ctx.rftab, rftab.data(), 8 * rftab.size());
+    if (!powtab.empty()) up.put(b->ctx.powtab, powtab.data(), 8 * powtab.size());
     b->psets_dev = pd;                                         // (host copy: which paramsets have a power table)
     b->rftab.swap(rftab);                                      // (host copy: RunAlgo's stem filters re-sum cells, sq_algos.hip)
-    if (!rbpk.empty()) UP(b->ctx.rbpk, rbpk.data(), 4 * rbpk.size());
-    {
-        // device tail: the first job of every sequence -- it needs each sequence's jobs contiguous, in sequence order, at
-        // most 64 of them (the paramset mask); any other job list keeps the host tail -- and pow(k / 2, 1.7) from the
-        // host's libm for ScoreStruct's stem terms (:884: sums of 4 / 1.5 / -0.5 per pair are multiples of 1/2)
-        std::vector<int32_t> sj0((size_t)d->nseq + 1, 0);
-        bool grouped = true;
-        int j = 0;
-        for (int sq = 0; sq < d->nseq; sq++) {
-            sj0[sq] = j;
-            while (j < d->njobs && d->job_seq[j] == sq) j++;
-            if (j == sj0[sq] || j - sj0[sq] > 64) grouped = false;
-        }
-        sj0[d->nseq] = j;
-        if (j != d->njobs) grouped = false;
-        if (grouped) UP(b->tail.seq_job0, sj0.data(), 4 * sj0.size());
-        else b->tail.seq_job0 = nullptr;
-        std::vector<double> pw((size_t)L.pow_len);
-        for (int k = 0; k < L.pow_len; k++) pw[k] = pow(0.5 * (double)k, 1.7);
-        UP(b->tail.pow17h, pw.data(), 8 * pw.size());
+    if (!rbpk.empty()) up.put(b->ctx.rbpk, rbpk.data(), 4 * rbpk.size());
+    return up.rc;
+}
+
+int BatchCreate::upload_tail_tables()
+{
+    // device tail: the first job of every sequence -- it needs each sequence's jobs contiguous, in sequence order, at
+    // most 64 of them (the paramset mask); any other job list keeps the host tail -- and pow(k / 2, 1.7) from the
+    // host's libm for ScoreStruct's stem terms (:884: sums of 4 / 1.5 / -0.5 per pair are multiples of 1/2)
+    std::vector<int32_t> sj0((size_t)d->nseq + 1, 0);
+    bool grouped = true;
+    int j = 0;
+    for (int sq = 0; sq < d->nseq; sq++) {
+        sj0[sq] = j;
+        while (j < d->njobs && d->job_seq[j] == sq) j++;
+        if (j == sj0[sq] || j - sj0[sq] > 64) grouped = false;
     }
+    sj0[d->nseq] = j;
+    if (j != d->njobs) grouped = false;
+    if (grouped) up.put(b->tail.seq_job0, sj0.data(), 4 * sj0.size());
+    else b->tail.seq_job0 = nullptr;
+    std::vector<double> pw((size_t)L.pow_len);
+    for (int k = 0; k < L.pow_len; k++) pw[k] = pow(0.5 * (double)k, 1.7);
+    up.put(b->tail.pow17h, pw.data(), 8 * pw.size());
+    return up.rc;
+}
+
+int BatchCreate::upload_caller_matrices()
+{
     for (int j = 0; j < d->njobs; j++) {
         const SqJob &J = b->jobs[j];
         const size_t nn = (size_t)J.n * J.n * 8;
         if (J.has_ext == 1) {
-            if (!d->ext_bool || !d->ext_bool[j]) { hipStreamSynchronize(st); delete b; sq_set_error("ext_score without ext_bool"); return -1; }
-            UP(b->ctx.mat64 + J.mat64_off, d->ext_score[j], nn);
-            UP(b->ctx.mat64 + J.mat64_off + (int64_t)J.n * J.n, d->ext_bool[j], nn);
+            if (!d->ext_bool || !d->ext_bool[j]) { sq_set_error("ext_score without ext_bool"); return -1; }
+            up.put(b->ctx.mat64 + J.mat64_off, d->ext_score[j], nn);
+            up.put(b->ctx.mat64 + J.mat64_off + (int64_t)J.n * J.n, d->ext_bool[j], nn);
         } else if (J.has_ext == 2 && !(d->mul_shared && d->mul_shared[j])) {
-            UP(b->ctx.mat64 + J.mat64_off, (d->bpp_term && d->bpp_term[j]) ? d->bpp_term[j] : d->mul_score[j], nn);
+            up.put(b->ctx.mat64 + J.mat64_off, (d->bpp_term && d->bpp_term[j]) ? d->bpp_term[j] : d->mul_score[j], nn);
         }
     }
-    if (d->mul_matrix_dev && d->mul_shared) {
-        // jobs weighted by the shared L x L matrix: the kernels read it through the column maps (sq_mulsh_weight) from a
-        // diagonal-major copy; SQ_MUL_GATHER=1: their N x N slices are gathered from it here
-        int32_t *d_cols = (int32_t *)(base + L.off_mulcols);
-        b->ctx.mulM = (double *)(base + L.off_mulM); b->ctx.mulcols = d_cols; b->ctx.mulL = d->mul_L;
-        sq_launch_mul_diag((const double *)d->mul_matrix_dev, d->mul_L, (double *)(base + L.off_mulM), st);
-        for (int64_t q = 0; q < L.ltot; q++)
-            if (d->mul_cols[q] < 0 || d->mul_cols[q] >= d->mul_L) { hipStreamSynchronize(st); delete b; sq_set_error("mul_cols out of range"); return -1; }
-        UP(d_cols, d->mul_cols, 4 * (size_t)L.ltot);
-        std::vector<int32_t> jl;
-        for (int j = 0; j < d->njobs; j++) if (d->mul_shared[j] && !b->jobs[j].mulsh) jl.push_back(j);
-        if (!jl.empty()) {
-            // (the job list travels in the candidate arena's first bytes: nothing else uses it before the first fold)
-            int32_t *d_jl = (int32_t *)(base + L.off_cands);
-            UP(d_jl, jl.data(), 4 * jl.size());
-            sq_launch_gather_mul(b->ctx, d_jl, (int)jl.size(), L.maxn, st);
-            if (sq_check(hipGetLastError(), "sq_gather_mul_kernel")) { hipStreamSynchronize(st); delete b; return 2; }
-        }
+    return up.rc;
+}
+
+int BatchCreate::upload_shared_matrix()
+{
+    if (!d->mul_matrix_dev || !d->mul_shared) return 0;
+    hipStream_t st = b->stream;
+    // jobs weighted by the shared L x L matrix: the kernels read it through the column maps (sq_mulsh_weight) from a
+    // diagonal-major copy; SQ_MUL_GATHER=1: their N x N slices are gathered from it here
+    int32_t *d_cols = at<int32_t>(base, L.off_mulcols);
+    b->ctx.mulM = at<double>(base, L.off_mulM); b->ctx.mulcols = d_cols; b->ctx.mulL = d->mul_L;
+    sq_launch_mul_diag((const double *)d->mul_matrix_dev, d->mul_L, at<double>(base, L.off_mulM), st);
+    for (int64_t q = 0; q < L.ltot; q++)
+        if (d->mul_cols[q] < 0 || d->mul_cols[q] >= d->mul_L) { sq_set_error("mul_cols out of range"); return -1; }
+    up.put(d_cols, d->mul_cols, 4 * (size_t)L.ltot);
+    std::vector<int32_t> jl;
+    for (int j = 0; j < d->njobs; j++) if (d->mul_shared[j] && !b->jobs[j].mulsh) jl.push_back(j);
+    if (!jl.empty()) {
+        // (the job list travels in the candidate arena's first bytes: nothing else uses it before the first fold)
+        int32_t *d_jl = at<int32_t>(base, L.off_cands);
+        if (up.put(d_jl, jl.data(), 4 * jl.size())) return up.rc;     // (no gather over a list that did not arrive)
+        sq_launch_gather_mul(b->ctx, d_jl, (int)jl.size(), L.maxn, st);
+        if (sq_check(hipGetLastError(), "sq_gather_mul_kernel")) return 2;
     }
-#undef UP
-    // pinned staging
-#ifdef SQ_CREATE_PROF
-    _cp.emplace_back("uploads", now_s());
-#endif
+    return up.rc;
+}
+
+// ---- pinned staging ----
+int BatchCreate::pinned_buffers()
+{
     if (sq_pinned_get((void **)&b->h_structs, sizeof(SqStruct) * L.max_structs) ||
         sq_pinned_get((void **)&b->h_strands, sizeof(SqStrand) * (size_t)L.strand_cap) ||
         sq_pinned_get((void **)&b->h_ctr, sizeof(SqCounters)) ||
-        sq_pinned_get((void **)&b->h_seq, 64)) { delete b; return 2; }
+        sq_pinned_get((void **)&b->h_seq, 64)) return 2;
     *b->h_seq = 0; b->round_seq = 0;
     b->h_out_cap = (uint32_t)std::min<uint64_t>(1u << 18, L.out_cap);
     if (sq_pinned_get((void **)&b->h_out, sizeof(SqOut) * (size_t)b->h_out_cap) ||
         sq_pinned_get((void **)&b->h_ctr2, sizeof(SqCounters)) ||
-        sq_pinned_get((void **)&b->h_seq2, 64)) { delete b; return 2; }
+        sq_pinned_get((void **)&b->h_seq2, 64)) return 2;
     // (cached buffers come back with their old contents: the completion words must not look like a finished round)
     memset(b->h_ctr, 0, sizeof(SqCounters)); memset(b->h_ctr2, 0, sizeof(SqCounters));
     memset(b->h_seq, 0, 64); memset(b->h_seq2, 0, 64);
     *b->h_seq2 = 0;
-    {   // the lane that spans all round buffers, and its two halves
-        SqLane &F = b->lane_full;
-        F.h_structs = b->h_structs; F.h_strands = b->h_strands; F.h_out = b->h_out; F.h_ctr = b->h_ctr; F.h_seq = b->h_seq;
-        F.d_structs = b->d_structs; F.d_strands = b->d_strands; F.d_out = b->d_out; F.d_ctr = b->scan.ctr;
-        F.h_out_cap = b->h_out_cap; F.out_cap = b->out_cap; F.slot0 = 0; F.max_structs = b->max_structs;
-        F.strand_cap = b->strand_cap; F.cand0 = 0; F.cand_records = b->cand_records;
-        F.round_seq = &b->round_seq;
-        for (int k = 0; k < 2; k++) {
-            SqLane &H = b->lane_half[k];
-            const int ms0 = b->max_structs / 2, sc0 = b->strand_cap / 2;
-            const uint32_t ho0 = b->h_out_cap / 2, oc0 = b->out_cap / 2;
-            H.slot0 = k ? ms0 : 0; H.max_structs = k ? b->max_structs - ms0 : ms0;
-            H.h_structs = b->h_structs + H.slot0; H.d_structs = b->d_structs + H.slot0;
-            H.strand_cap = k ? b->strand_cap - sc0 : sc0;
-            H.h_strands = b->h_strands + (k ? sc0 : 0); H.d_strands = b->d_strands + (k ? sc0 : 0);
-            H.h_out_cap = k ? b->h_out_cap - ho0 : ho0; H.out_cap = k ? b->out_cap - oc0 : oc0;
-            H.h_out = b->h_out + (k ? ho0 : 0); H.d_out = b->d_out + (k ? oc0 : 0);
-            H.h_ctr = k ? b->h_ctr2 : b->h_ctr; H.h_seq = k ? b->h_seq2 : b->h_seq;
-            H.round_seq = k ? &b->round_seq2 : &b->round_seq;   // (one counter per completion word)
-            H.d_ctr = (SqCounters *)((char *)b->scan.ctr + (k ? 64 : 0));
-        }
+    return 0;
+}
+
+// the lane that spans all round buffers, and its two halves
+void set_lanes(sq_batch *b)
+{
+    SqLane &F = b->lane_full;
+    F.h_structs = b->h_structs; F.h_strands = b->h_strands; F.h_out = b->h_out; F.h_ctr = b->h_ctr; F.h_seq = b->h_seq;
+    F.d_structs = b->d_structs; F.d_strands = b->d_strands; F.d_out = b->d_out; F.d_ctr = b->scan.ctr;
+    F.h_out_cap = b->h_out_cap; F.out_cap = b->out_cap; F.slot0 = 0; F.max_structs = b->max_structs;
+    F.strand_cap = b->strand_cap; F.cand0 = 0; F.cand_records = b->cand_records;
+    F.round_seq = &b->round_seq;
+    for (int k = 0; k < 2; k++) {
+        SqLane &H = b->lane_half[k];
+        const int ms0 = b->max_structs / 2, sc0 = b->strand_cap / 2;
+        const uint32_t ho0 = b->h_out_cap / 2, oc0 = b->out_cap / 2;
+        H.slot0 = k ? ms0 : 0; H.max_structs = k ? b->max_structs - ms0 : ms0;
+        H.h_structs = b->h_structs + H.slot0; H.d_structs = b->d_structs + H.slot0;
+        H.strand_cap = k ? b->strand_cap - sc0 : sc0;
+        H.h_strands = b->h_strands + (k ? sc0 : 0); H.d_strands = b->d_strands + (k ? sc0 : 0);
+        H.h_out_cap = k ? b->h_out_cap - ho0 : ho0; H.out_cap = k ? b->out_cap - oc0 : oc0;
+        H.h_out = b->h_out + (k ? ho0 : 0); H.d_out = b->d_out + (k ? oc0 : 0);
+        H.h_ctr = k ? b->h_ctr2 : b->h_ctr; H.h_seq = k ? b->h_seq2 : b->h_seq;
+        H.round_seq = k ? &b->round_seq2 : &b->round_seq;   // (one counter per completion word)
+        H.d_ctr = (SqCounters *)((char *)b->scan.ctr + (k ? 64 : 0));
     }
-#ifdef SQ_CREATE_PROF
-    _cp.emplace_back("pinned+kernels", now_s());
-#endif
-    int rr = sq_check(hipStreamSynchronize(st), "sync after upload");   // host vectors above go out of scope
-    if (rr) { delete b; return rr; }
-#ifdef SQ_CREATE_PROF
-    _cp.emplace_back("sync", now_s());
-    { std::string line = "[sq_batch_create ms]"; for (size_t k = 1; k < _cp.size(); k++) { char t[64]; snprintf(t, sizeof t, " %s %.2f", _cp[k].first, (_cp[k].second - _cp[k - 1].second) * 1e3); line += t; } fprintf(stderr, "%s\n", line.c_str()); }
-#endif
-    b->results.resize(d->nseq);
-    *out = b;
+}
+}  // namespace
+
+extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws, size_t ws_bytes, void *hip_stream)
+{
+    BatchCreate c;
+    c.d = d;
+    int rc = plan(d, c.L);
+    if (rc) return rc;
+    c.prof.mark("plan");
+    if ((rc = c.check_request(ws, ws_bytes))) return rc;
+    c.b = c.own.b = new sq_batch();
+    c.base = (char *)ws;
+    c.host_copies(hip_stream);
+    c.prof.mark("copies");
+    if ((rc = c.position_arrays())) return rc;
+    c.prof.mark("positions");
+    c.paramset_records();
+    c.reactivity_levels();
+    c.prof.mark("paramsets");
+    c.job_records();
+    if ((rc = c.check_against_plan())) return rc;
+    c.prof.mark("jobs");
+    c.carve();
+    if ((rc = c.open_uploads())) return rc;
+    c.prof.mark("carve");
+    if ((rc = c.upload_inputs()) || (rc = c.upload_tail_tables()) || (rc = c.upload_caller_matrices()) || (rc = c.upload_shared_matrix())) return rc;
+    c.prof.mark("uploads");
+    if ((rc = c.pinned_buffers())) return rc;
+    set_lanes(c.b);
+    c.prof.mark("pinned+kernels");
+    if ((rc = sq_check(hipStreamSynchronize(c.b->stream), "sync after upload"))) return rc;   // host vectors above go out of scope
+    c.prof.mark("sync");
+    c.prof.report();
+    c.b->results.resize(d->nseq);
+    *out = c.own.release();
     return 0;
 }
 
@@ -855,4 +989,3 @@ extern "C" void sq_batch_destroy(sq_batch *b)
         fprintf(stderr, "[sq_batch_destroy] %.1f ms: stream syncs %.1f, pinned buffers %.1f, pool + events %.1f, delete %.1f\n", (now_s() - td0) * 1e3,
                 (td1 - td0) * 1e3, (td2 - td1) * 1e3, (td3 - td2) * 1e3, (now_s() - td3) * 1e3);
 }
-

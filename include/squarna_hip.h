@@ -334,6 +334,32 @@ SQ_API int sq_result_view(const sq_batch *b, const void **buf, const int64_t **o
  * thousand were copied record by record, a quarter of the call).  Copy the offsets first: they stay the batch's. */
 SQ_API int sq_result_detach(sq_batch *b, void **buf, int64_t *nbytes);
 SQ_API void sq_buffer_release(void *buf);
+/* The same results as pair tables in the CALLER's device memory (no reference counterpart: a caller of SQRNdbnseq parses
+ * the bracket strings, DBNToPairs SQRNdbnseq.py:172-207) -- for code that goes on with them on the same GPU.  Field by field
+ * what sq_result_pack holds, brackets replaced by partners:
+ *   d_partner    int32: record s has 1 + nstruct[s] rows of n[s] entries from d_partner[d_cell_off[s]] on; row 0 is the
+ *                consensus (the top structure when the fold's conslim was 1; all -1 when it was 0 or the record has no
+ *                structure), rows 1.. the shown structures in rank order; entry i = the 0-based partner of position i, or
+ *                -1 (gap-free coordinates, as in the packed records)
+ *   d_scores     double[rows][3], d_pset_mask uint64[rows]: the structure rows only, record s from row d_row_off[s] on
+ *   d_metrics    double[nseq][16]: cons_metrics[6], best_metrics[7], ref_scores[3] (NaN without a known structure)
+ *   d_row_off, d_cell_off   int64[nseq + 1]: written here, the totals last
+ * nstruct[s] = d_row_off[s + 1] - d_row_off[s] is what sq_result_nstruct reports (sq_result_limit as for the packed getters).
+ * sq_result_pairs_size gives the totals a caller sizes its buffers with: rows = sum of nstruct, cells = sum of (1 + nstruct) n.
+ * Both return 0, or 1 when the last fold's results are not in the device tail's form -- the host tail ran (sq_fold_paths
+ * bit 0 clear), sq_result_limit shows fewer structures than were packed, or sq_result_detach took the records away: the
+ * caller then reads the packed records --, or -1 (bad argument; a capacity below what sq_result_pairs_size reports:
+ * nothing is written, sq_last_error names the sizes).  Not -3: that status is about the capacities a BATCH was created with
+ * (sq_last_capacity) and makes a caller repeat the fold with a larger batch, which does not help a buffer of the caller's;
+ * and not -(needed): two sizes are needed.  sq_result_pairs_size is the way to learn them -- call it first.
+ * The rows are formed by a kernel from the scratch the ranking tail left in the batch's workspace; nothing but the next
+ * sq_fold of the batch writes that scratch (no other entry point recycles it), so the call is valid, any number of times,
+ * from the return of sq_fold until the batch's next sq_fold or its destruction.  The library allocates nothing.
+ * Asynchronous: the work is enqueued on hip_stream (NULL: the batch's stream) and the call does not wait for it; it must
+ * be complete before the batch folds again. */
+SQ_API int sq_result_pairs_size(const sq_batch *b, int64_t *rows, int64_t *cells);
+SQ_API int sq_result_pairs_dev(sq_batch *b, int32_t *d_partner, int64_t cells_cap, double *d_scores, uint64_t *d_pset_mask,
+                               int64_t rows_cap, double *d_metrics, int64_t *d_row_off, int64_t *d_cell_off, void *hip_stream);
 /* Dot-bracket rows of every record as ASCII text: record s occupies [off[s], off[s+1]) of buf with its consensus row
  * and then its nstruct structure rows, n characters each (gap-free coordinates; gap columns and separators are
  * re-inserted by the caller, SQRNdbnseq.py:1239-1246).  Levels 1..30 print as ( [ { < A..Z and ) ] } > a..z (:107-112);

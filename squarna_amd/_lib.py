@@ -23,7 +23,7 @@ SYMBOLS = ["sq_version", "sq_last_error", "sq_last_capacity", "sq_batch_workspac
            "sq_align_accumulate", "sq_colmatrix_select", "sq_fold_concurrent", "sq_fold_concurrent_n", "sq_fold_driver", "sq_fold_paths", "sq_fold_peak_structs", "sq_result_limit",
            "sq_mwm_workspace_bytes", "sq_mwm", "sq_lsap_workspace_bytes", "sq_lsap",
            "sq_nussinov_workspace_bytes", "sq_nussinov", "sq_dbn_pairs", "sq_write_blocks", "sq_parse_default",
-           "sq_host_cache_trim", "sq_align_first_fit"]
+           "sq_host_cache_trim", "sq_align_first_fit", "sq_result_pairs_size", "sq_result_pairs_dev"]
 
 BATCH_NO_FP32 = 1
 BATCH_POOL_LISTS = 2
@@ -116,6 +116,9 @@ def load():
     L.sq_result_view.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.sq_result_detach.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.sq_buffer_release.argtypes = [C.c_void_p]
+    L.sq_result_pairs_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.sq_result_pairs_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]
     L.sq_buffer_release.restype = None
     L.sq_result_dbn_all_size.restype = C.c_int64
     L.sq_result_dbn_all_size.argtypes = [C.c_void_p]

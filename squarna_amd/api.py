@@ -23,6 +23,37 @@ BATCH_RECORDS = 16384                 # records folded in one GPU batch (bigger 
 BATCH_CELLS = 2 * 1024 * 1024 * 1024   # ... bounded by sum of N^2 x paramsets
 
 
+def _find_config(configfile, HOME_DIR, priority):
+    """(configuration file, whether the caller named one, priority names): SQUARNA.py:683-703.  No file named: def.conf (and, by
+    length, 500.conf / 1000.conf beside it) with the default priority paramsets."""
+    if configfile is None:
+        priority = set('bppN,bppH1,bppH2'.split(',')) if priority is None else {x for x in priority.split(',') if x}
+        return os.path.join(HOME_DIR, "def.conf"), False, priority
+    if not os.path.exists(configfile):
+        if os.path.exists(os.path.join(HOME_DIR, configfile + ".conf")):
+            configfile = os.path.join(HOME_DIR, configfile + ".conf")
+        elif os.path.exists(os.path.join(HOME_DIR, configfile)):
+            configfile = os.path.join(HOME_DIR, configfile)
+    assert os.path.exists(configfile), "Config file does not exist."
+    return configfile, True, set() if priority is None else {x for x in priority.split(',') if x}
+
+
+def _as_int(value, what, check, label):
+    try:
+        value = int(float(value))
+        assert check(value)
+        return value
+    except Exception:
+        raise ValueError("Inappropriate {} value ({}): {}".format(what, label, value))
+
+
+def _rank_keys(rankby):
+    """(rankbydiff, the order of the three scores) of a validated rankby string: SQUARNA.py:810-820."""
+    if "r" in rankby and "s" in rankby:
+        return "d" in rankby, (0, 2, 1)
+    return "d" in rankby, (2, 0, 1) if "r" in rankby else (1, 2, 0)
+
+
 def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, inputformat="qtrf",
             maxstemnum=None, threads=os.cpu_count(), byseq=False, algorithms='', entropy=False,
             rankby="r", evalonly=False, hardrest=False, interchainonly=False, toplim=5, outplim=None,
@@ -64,34 +95,15 @@ def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
     assert os.path.exists(str(inputfile)) or inputseq, "Input file does not exist."
     assert fileformat in {'unknown', 'fasta', 'default', 'stockholm', 'clustal'}, \
         "Wrong fileformat, choose one of these: default,fasta,stockholm,clustal"
-    if configfile is None:
-        configfileset = False
-        configfile = os.path.join(HOME_DIR, "def.conf")
+    configfile, configfileset, priority = _find_config(configfile, HOME_DIR, priority)
+    if not configfileset:
         configfile500 = os.path.join(HOME_DIR, "500.conf")
         configfile1000 = os.path.join(HOME_DIR, "1000.conf")
-        priority = set('bppN,bppH1,bppH2'.split(',')) if priority is None else {x for x in priority.split(',') if x}
-    else:
-        configfileset = True
-        if not os.path.exists(configfile):
-            if os.path.exists(os.path.join(HOME_DIR, configfile + ".conf")):
-                configfile = os.path.join(HOME_DIR, configfile + ".conf")
-            elif os.path.exists(os.path.join(HOME_DIR, configfile)):
-                configfile = os.path.join(HOME_DIR, configfile)
-        assert os.path.exists(configfile), "Config file does not exist."
-        priority = set() if priority is None else {x for x in priority.split(',') if x}
     assert ''.join(sorted(inputformat.replace('x', ''))) in {"q", "fq", "qr", "qt", "qrt", "fqr", "fqt", "fqrt"}, \
         'Inappropriate inputformat value (subset of "fqrtx" with "q" being mandatory): {}'.format(inputformat)
 
-    def as_int(value, what, check, label):
-        try:
-            value = int(float(value))
-            assert check(value)
-            return value
-        except Exception:
-            raise ValueError("Inappropriate {} value ({}): {}".format(what, label, value))
-
     maxstemnumset = maxstemnum is not None
-    maxstemnum = as_int(maxstemnum, "maxstemnum", lambda x: x >= 0, "non-negative integer") if maxstemnumset else 10 ** 6
+    maxstemnum = _as_int(maxstemnum, "maxstemnum", lambda x: x >= 0, "non-negative integer") if maxstemnumset else 10 ** 6
     try:
         threads = min(max(1, int(float(threads))), os.cpu_count())
     except Exception:
@@ -113,12 +125,12 @@ def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
         'Inappropriate rankby value (r/s/rs/dr/ds/drs): {}'.format(rankby)
     outplimset = outplim is not None
     if outplimset:
-        outplim = as_int(outplim, "outplim", lambda x: x > 0, "positive integer")
-    toplim = as_int(toplim, "toplim", lambda x: x > 0, "positive integer")
+        outplim = _as_int(outplim, "outplim", lambda x: x > 0, "positive integer")
+    toplim = _as_int(toplim, "toplim", lambda x: x > 0, "positive integer")
     if not outplimset:
         outplim = toplim
-    conslim = as_int(conslim, "conslim", lambda x: x > 0, "positive integer")
-    poollim = as_int(poollim, "poollim", lambda x: x > 0, "positive integer")
+    conslim = _as_int(conslim, "conslim", lambda x: x > 0, "positive integer")
+    poollim = _as_int(poollim, "poollim", lambda x: x > 0, "positive integer")
     assert int(float(reactformat)) in {3, 10, 26}, "Inappropriate reactformat value (3/10/26): {}".format(reactformat)
     reactformat = int(float(reactformat))
     if levellimit is not None:
@@ -137,13 +149,7 @@ def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
     except Exception:
         raise ValueError("Inappropriate freqlimit value (float between 0.0 and 1.0): {}".format(step3))
 
-    rankbydiff = "d" in rankby                                   # SQUARNA.py:810-820
-    if "r" in rankby and "s" in rankby:
-        rankby = (0, 2, 1)
-    elif "r" in rankby:
-        rankby = (2, 0, 1)
-    elif "s" in rankby:
-        rankby = (1, 2, 0)
+    rankbydiff, rankby = _rank_keys(rankby)
 
     if alignment and not configfileset:                          # SQUARNA.py:822-824
         configfile = os.path.join(HOME_DIR, "ali.conf")

@@ -514,6 +514,40 @@ class Batch:
         _lib.check(self.L.sq_result_pack_all(self.h, _ptr(buf), nbytes, _ptr(off)))
         return buf[:nbytes], off
 
+    def result_tensors(self):
+        """The last fold's results as torch tensors on the batch's device (sq_result_pairs_dev): dict of
+        partner int32[cells], scores float64[rows, 3], pset_mask int64[rows] (the uint64 masks' bit patterns),
+        metrics float64[nseq, 16], row_off / cell_off int64[nseq + 1] -- the layout of include/squarna_hip.h, gap-free
+        coordinates.  None when the results are not in the device tail's form (the host tail ran): pack_all then.
+        Enqueued on the batch's stream; the tensors are the caller's and outlive the batch."""
+        torch = self.torch
+        rows, cells = C.c_int64(), C.c_int64()
+        rc = self.L.sq_result_pairs_size(self.h, C.byref(rows), C.byref(cells))
+        if rc == 1:
+            return None
+        _lib.check(rc)
+        rows, cells = int(rows.value), int(cells.value)
+        with torch.cuda.stream(self.stream):
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+            # (at least one element each: an empty tensor has no address to pass)
+            out = dict(partner=new(max(cells, 1), torch.int32)[:cells], scores=new((max(rows, 1), 3), torch.float64)[:rows],
+                       pset_mask=new(max(rows, 1), torch.int64)[:rows], metrics=new((max(self.nseq, 1), 16), torch.float64)[:self.nseq],
+                       row_off=new(self.nseq + 1, torch.int64), cell_off=new(self.nseq + 1, torch.int64))
+        rc = self.L.sq_result_pairs_dev(self.h, out["partner"].data_ptr(), cells, out["scores"].data_ptr(), out["pset_mask"].data_ptr(),
+                                        rows, out["metrics"].data_ptr(), out["row_off"].data_ptr(), out["cell_off"].data_ptr(),
+                                        C.c_void_p(self.stream.cuda_stream))
+        if rc == 1:
+            return None
+        _lib.check(rc)
+        return out
+
+    def result_counts(self):
+        """(nstruct, lengths) of every record as host int64 arrays -- the sizes behind result_tensors' offsets, read from the
+        headers of the packed records (no device round trip)."""
+        buf, off = self.pack_all()
+        q = np.frombuffer(buf, '<i8', len(buf) // 8)
+        return q[off[:-1] // 8].astype(np.int64), np.diff(self.seq_off).astype(np.int64)
+
     def detach_packed(self):
         """The packed results of every record as read-only memoryviews of the library's pinned buffer, which leaves the batch
         with them (sq_result_detach): no copy; the buffer goes back to the library when the last view is dropped.  None when

@@ -211,6 +211,7 @@ struct sq_batch {
     bool packed_ok = false;               // the last fold's results are the packed records above (else: `results`)
     int tail_maxshow = 0;                 // most structures shown for one sequence in the last device tail (shapes the next pack launch)
     int32_t packed_limit = 0;             // result_limit in force at that fold
+    int32_t packed_conslim = 1;           // conslim of that fold (0 or 1: sq_result_pairs_dev forms the consensus row again)
     // profiling
     std::mutex mwm_mu;
     int64_t mwm_stats[6] = {0, 0, 0, 0, 0, 0};   // blossom jobs collected, their scan passes; the job with the most passes:
@@ -305,6 +306,9 @@ void sq_algos_abandon(sq_batch *b, SqAlgoAsync *pa);      // error paths: waits 
 // Returns 0: the packed results are in place (b->packed_ok), 1: the batch needs the host tail (nothing changed), else an error.
 int sq_tail_device(sq_batch *b, const sq_fold_opts &o, const int32_t *ref_off, const int32_t *ref_pairs, const uint8_t *has_ref);
 int sq_tail_refs(sq_batch *b, const int32_t *ref_off, const int32_t *ref_pairs, const uint8_t *has_ref);
+// the kernels of sq_result_pairs_dev on `st`: the device tail's results as partner arrays in the caller's device memory
+int sq_tail_pairs_launch(sq_batch *b, int32_t *d_partner, double *d_scores, uint64_t *d_pset_mask, double *d_metrics, int64_t *d_row_off,
+                         int64_t *d_cell_off, hipStream_t st);
 // whether the options of this fold are covered by the device tail at all
 bool sq_tail_device_wanted(const sq_batch *b, const sq_fold_opts &o);
 

@@ -197,6 +197,35 @@ extern "C" int sq_result_detach(sq_batch *b, void **buf, int64_t *nbytes)
 }
 extern "C" void sq_buffer_release(void *buf) { sq_pinned_put(buf); }
 
+// ---- the same results as pair tables in the caller's DEVICE memory --------------------------------------------------
+// Formed by sq_tail_pairs_kernel from the scratch the device tail left in the workspace (nothing but the next sq_fold
+// writes it), so only while the packed records above are the fold's results and show what the fold packed.
+static inline bool pairs_ready(const sq_batch *b) { return b->packed_ok && packed_whole(b) && b->h_rec && b->h_rec_off && b->h_txt_off; }
+extern "C" int sq_result_pairs_size(const sq_batch *b, int64_t *rows, int64_t *cells)
+{
+    if (!b || !rows || !cells) { sq_set_error("bad argument"); return -1; }
+    if (!pairs_ready(b)) return 1;
+    int64_t r = 0;
+    for (int s = 0; s < b->nseq; s++) r += packed_rec(b, s).ns;
+    *rows = r; *cells = (int64_t)b->h_txt_off[b->nseq];            // (a text row has a character per position: the same count)
+    return 0;
+}
+extern "C" int sq_result_pairs_dev(sq_batch *b, int32_t *d_partner, int64_t cells_cap, double *d_scores, uint64_t *d_pset_mask, int64_t rows_cap,
+                                   double *d_metrics, int64_t *d_row_off, int64_t *d_cell_off, void *stream)
+{
+    if (!b || !d_partner || !d_scores || !d_pset_mask || !d_metrics || !d_row_off || !d_cell_off) { sq_set_error("bad argument"); return -1; }
+    int64_t rows = 0, cells = 0;
+    const int r = sq_result_pairs_size(b, &rows, &cells);
+    if (r) return r;
+    if (cells > cells_cap || rows > rows_cap) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "pair buffers too small: %lld rows and %lld cells needed", (long long)rows, (long long)cells);
+        sq_set_error(msg);
+        return -1;
+    }
+    return sq_tail_pairs_launch(b, d_partner, d_scores, d_pset_mask, d_metrics, d_row_off, d_cell_off, stream ? (hipStream_t)stream : b->stream);
+}
+
 // Dot-bracket rows of every record as ASCII text (the bulk form of levels -> characters): record s occupies
 // [off[s], off[s+1]) with its consensus row and then its nstruct structure rows, n characters each (gap-free
 // coordinates, no separators re-inserted: the caller does that for the records that have any).  Levels 1..30 print as

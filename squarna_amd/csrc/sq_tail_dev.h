@@ -7,6 +7,9 @@
 // as ASCII text, written by the kernels straight into pinned host memory: after a fold the host holds the bytes
 // sq_result_pack_all / sq_result_dbn_all hand out, and no per-sequence host code has run.
 //
+// The scratch the ranking kernel leaves (seqs, rlist, ord, cstems, cs_n, scores, mask) has regions of its own in the workspace and
+// is written by nothing but the next fold: sq_result_pairs_dev reads it again for the same results as partner arrays.
+//
 // What the device path does not cover falls back to the host tail (sq_tail.cpp) for the whole batch, with identical
 // results: rankbydiff, hardrest with forced pairs, conslim > 1, more than SQ_TAIL_MAXM final structures for one sequence,
 // stem lists that are not disjoint stacks, scores beyond the exact range of sq_round3.
@@ -75,6 +78,9 @@ __global__ void sq_tail_scatter_kernel(SqTailIO t);
 __global__ void sq_tail_rank_kernel(SqDevCtx c, SqTailIO t, int bitwords, int keycap, int refp_lds);
 __global__ void sq_tail_offsets_kernel(SqTailIO t, volatile uint32_t *h_seq, uint32_t seq);
 __global__ void sq_tail_pack_kernel(SqDevCtx c, SqTailIO t, int rowcap, long long rec_cap, long long txt_cap);
+__global__ void sq_tail_pairs_off_kernel(SqDevCtx c, SqTailIO t, long long *row_off, long long *cell_off);
+__global__ void sq_tail_pairs_kernel(SqDevCtx c, SqTailIO t, int32_t *partner, double *scores, unsigned long long *masks, double *metrics,
+                                     const long long *row_off, const long long *cell_off);
 __global__ void sq_fold_begin_kernel(uint32_t *fin_ctr, long long *job_evals, uint32_t *job_cnt, int njobs);
 __global__ void sq_fin_keep_algos_kernel(SqPoolFin *fin, uint32_t *fin_ctr, uint32_t fin_cap, long long *job_evals, uint32_t *job_cnt, int njobs);
 __global__ void sq_tail_done_kernel(SqTailIO t, long long *h_rec_off, long long *h_txt_off, volatile uint32_t *h_seq, uint32_t seq);

@@ -12,6 +12,10 @@
 //   sq_tail_pack_kernel              one wave per (sequence, slice of its shown structures): pseudoknot levels at stem
 //                                    level (sq_stem_levels_wave), the int16 level rows and the ASCII rows, header, scores,
 //                                    masks, metrics -- written straight into pinned host memory in the C ABI's layout
+// and, when the caller asks for the results as data in ITS device memory (sq_result_pairs_dev), after the fold:
+//   sq_tail_pairs_off_kernel         one block: where every record's rows and cells start
+//   sq_tail_pairs_kernel             one wave per (sequence, slice of its shown structures): partner arrays from the
+//                                    canonical stems, scores, masks, metrics
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/squarna_hip.h"
@@ -737,6 +741,98 @@ extern "C" __global__ __launch_bounds__(1024) void sq_tail_done_kernel(SqTailIO 
     }
 }
 
+// ---- pair tables in the caller's device memory (sq_result_pairs_dev) -------------------------------------------------
+// What the pack kernel turns into bracket levels and text, as data: per record 1 + nshow rows of n partners (-1: unpaired),
+// the scores / masks of the shown structures and the metrics block.  Both kernels read the scratch the ranking kernel left
+// (seqs, rlist, ord, the canonical stems, scores, mask): nothing but the next sq_fold of the batch writes it.
+//
+// one block: where every record's rows and cells start (nseq + 1 entries each, the totals last)
+extern "C" __global__ __launch_bounds__(1024) void sq_tail_pairs_off_kernel(SqDevCtx c, SqTailIO t, long long *row_off, long long *cell_off)
+{
+    __shared__ long long s_a[1024], s_b[1024];
+    const int tid = threadIdx.x, n = t.nseq;
+    const int ipt = (n + 1023) / 1024;
+    const int lo = min(tid * ipt, n), hi = min(lo + ipt, n);
+    long long a = 0, b = 0;
+    for (int q = lo; q < hi; q++) { const long long ns = t.seqs[q].nshow; a += ns; b += (1 + ns) * c.jobs[t.seq_job0[q]].n; }
+    s_a[tid] = a; s_b[tid] = b;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const long long va = tid >= d ? s_a[tid - d] : 0, vb = tid >= d ? s_b[tid - d] : 0;
+        __syncthreads();
+        s_a[tid] += va; s_b[tid] += vb;
+        __syncthreads();
+    }
+    long long ra = s_a[tid] - a, rb = s_b[tid] - b;
+    for (int q = lo; q < hi; q++) {
+        const long long ns = t.seqs[q].nshow;
+        row_off[q] = ra; cell_off[q] = rb;
+        ra += ns; rb += (1 + ns) * c.jobs[t.seq_job0[q]].n;
+    }
+    if (tid == 1023) { row_off[n] = s_a[1023]; cell_off[n] = s_b[1023]; }
+}
+
+// grid (nseq, Y) like the pack kernel: block (s, y) is one wave and forms the rows of structures y, y + Y, ... of sequence
+// s; y == 0 also writes the consensus row when it is not the top structure, the scores / masks and the metrics.  A row is
+// built in LDS -- filled with -1, then every canonical stem scatters its pairs (the stems of one structure are disjoint: no
+// two lanes write one position) -- and leaves with 16-byte stores from the first 16-byte boundary of its place on (a row
+// starts wherever the rows before it end: 4-byte aligned).  No crossing weights, no levels: a partner array has none.
+extern "C" __global__ __launch_bounds__(64) void sq_tail_pairs_kernel(SqDevCtx c, SqTailIO t, int32_t *partner, double *scores, unsigned long long *masks,
+                                                                      double *metrics, const long long *row_off, const long long *cell_off)
+{
+    extern __shared__ __attribute__((aligned(16))) int32_t sq_pairs_row[];   // [n rounded up to 4]
+    int32_t *const row = sq_pairs_row;
+    const int s = blockIdx.x, y = blockIdx.y, Y = gridDim.y, lane = threadIdx.x;
+    const SqTailSeq S = t.seqs[s];
+    const int n = c.jobs[t.seq_job0[s]].n;
+    const uint32_t first = S.first, ns = S.nshow;
+    int32_t *const rows = partner + cell_off[s];
+    auto put_row = [&](size_t r) {                                       // the LDS row -> row r of the record
+        int32_t *dst = rows + r * (size_t)n;
+        const int head = min(n, (int)((4u - (uint32_t)((reinterpret_cast<uintptr_t>(dst) >> 2) & 3u)) & 3u));
+        if (lane < head) dst[lane] = row[lane];
+        const int nv = (n - head) >> 2;
+        for (int q = lane; q < nv; q += 64) {
+            const int i = head + 4 * q;
+            *reinterpret_cast<int4 *>(dst + i) = make_int4(row[i], row[i + 1], row[i + 2], row[i + 3]);
+        }
+        const int done = head + 4 * nv;
+        if (lane < n - done) dst[done + lane] = row[done + lane];
+    };
+    for (uint32_t r = y; r < ns; r += Y) {
+        const uint32_t x = t.rlist[first + r];
+        const SqPoolStem *cs = sq_fin_canon(t, t.fin[t.ord[first + x]]);
+        const int T = (int)t.cs_n[first + x];
+        for (int i = lane; i < n; i += 64) row[i] = -1;
+        __syncthreads();
+        for (int q = lane; q < T; q += 64) {
+            const SqPoolStem st = cs[q];
+            for (int k = 0; k < st.len; k++) {
+                const int v = st.i + k, w = st.j - k;
+                if ((unsigned)v < (unsigned)n && (unsigned)w < (unsigned)n) { row[v] = w; row[w] = v; }
+            }
+        }
+        __syncthreads();
+        put_row((size_t)r + 1);
+        if (r == 0 && t.conslim == 1) put_row(0);                       // the consensus is the top structure (:1236)
+        __syncthreads();
+    }
+    if (y == 0) {
+        if (ns == 0 || t.conslim != 1) {                                // no structure (or conslim == 0): an empty consensus
+            for (int i = lane; i < n; i += 64) row[i] = -1;
+            __syncthreads();
+            put_row(0);
+        }
+        if (lane < 16) metrics[16 * (size_t)s + lane] = t.scores[3 * (size_t)t.fin_cap + 16 * (size_t)s + lane];
+        const long long r0 = row_off[s];
+        for (uint32_t r = lane; r < ns; r += 64) {
+            const uint32_t x = t.rlist[first + r];
+            for (int q = 0; q < 3; q++) scores[3 * (size_t)(r0 + r) + q] = t.scores[3 * (size_t)(first + x) + q];
+            masks[r0 + r] = t.mask[first + x];
+        }
+    }
+}
+
 // start of a fold: the log of final structures, the per-job evaluation counts and the tail's per-job counters start empty
 extern "C" __global__ __launch_bounds__(256) void sq_fold_begin_kernel(uint32_t *fin_ctr, long long *job_evals, uint32_t *job_cnt, int njobs)
 {
@@ -966,6 +1062,26 @@ int sq_tail_device(sq_batch *b, const sq_fold_opts &o, const int32_t *ref_off, c
         if (b->h_tail_totals[2] || b->h_tail_totals[5]) return 1;
     }
     b->h_rec_off[b->nseq] = (long long)rec_bytes; b->h_txt_off[b->nseq] = (long long)txt_bytes;
-    b->packed_ok = true; b->packed_limit = b->result_limit;
+    b->packed_ok = true; b->packed_limit = b->result_limit; b->packed_conslim = o.conslim;
     return 0;
+}
+
+// The launches of sq_result_pairs_dev (sq_results.hip checks the state and the capacities first): offsets, then the rows.
+int sq_tail_pairs_launch(sq_batch *b, int32_t *d_partner, double *d_scores, uint64_t *d_pset_mask, double *d_metrics, int64_t *d_row_off,
+                         int64_t *d_cell_off, hipStream_t st)
+{
+    SqTailIO t = b->tail;
+    t.conslim = b->packed_conslim;
+    // (coordinates are int16: a row is at most 128 KB and always fits the LDS of a CU)
+    const size_t dyn = (((size_t)b->maxn + 3) & ~(size_t)3) * 4 + 16;
+    if (dyn > 160 * 1024) { sq_set_error("a row of partners does not fit the LDS"); return -1; }
+    if (dyn > 64 * 1024) sq_max_dynamic_lds((const void *)sq_tail_pairs_kernel, 160 * 1024);
+    static_assert(sizeof(long long) == sizeof(int64_t), "offsets are 64-bit");
+    long long *ro = reinterpret_cast<long long *>(d_row_off), *co = reinterpret_cast<long long *>(d_cell_off);
+    hipLaunchKernelGGL(sq_tail_pairs_off_kernel, dim3(1), dim3(1024), 0, st, b->ctx, t, ro, co);
+    const int Y = std::max(1, std::min({std::max(b->tail_maxshow, 1), 64, std::max(1, 8192 / std::max(b->nseq, 1))}));
+    if (b->nseq > 0)
+        hipLaunchKernelGGL(sq_tail_pairs_kernel, dim3(b->nseq, Y), dim3(64), dyn, st, b->ctx, t, d_partner, d_scores,
+                           reinterpret_cast<unsigned long long *>(d_pset_mask), d_metrics, ro, co);
+    return sq_check(hipGetLastError(), "pair table launch");
 }

@@ -18,17 +18,17 @@ from .dbn import gap_mask
 # every name callers outside this module take from `engine` (bench.py, tests/, tools/, api.py, align.py, core.py, parallel.py)
 from .records import Prepared, PackedRows  # noqa: F401
 from .batch import Batch, fold_concurrently
-from .results import unpack_result, _Blocks, _BlockRun  # noqa: F401
+from .results import unpack_result, packed_pair_tables, _Blocks, _BlockRun  # noqa: F401
 from .bpp import vienna_bpp, set_bpp_provider, bpp_terms  # noqa: F401
 from .plan import (pool_slots_wanted, pool_slots_wanted_many, pool_slot_cap, slot_bytes, default_structs,  # noqa: F401
                    MIN_CAND_PER_NT, SubBatchPlan, _kept_bytes_per_slot, _free_device_bytes, _shared_weights)
 
 
-def _cut_in_two_lanes(groups, hints):
+def _cut_in_two_lanes(groups, hints, tensors=False):
     """SQ_ENGINE_LANES=2 and one big group: (groups, hints, back) with the group cut into two concurrent batches, back = the
     records' places (for one-shot calls the second batch's set-up costs more than the overlap saves, so that is opt-in);
-    else the arguments and None."""
-    if len(groups) == 1 and switches.engine_lanes() >= 2 and len(groups[0]) >= 256 and hints[0] is None:
+    else the arguments and None.  tensors: the results are whole-batch tables (fold_tensors), which are not cut."""
+    if len(groups) == 1 and switches.engine_lanes() >= 2 and len(groups[0]) >= 256 and hints[0] is None and not tensors:
         recs = groups[0]
         cost = [float(len(r[0])) ** 2 * len(r[4]) for r in recs]
         if sum(cost) >= 1e8 and not any(len(r) > 5 and r[5] is not None and hasattr(r[5], "is_cuda") for r in recs):
@@ -80,6 +80,71 @@ def _block_results(batches, groups, cfg):
     return res
 
 
+_TABLES = ("partner", "scores", "pset_mask", "metrics", "row_off", "cell_off")
+
+
+class _TensorRun:
+    """fold_records(_tensors=True) result of one batch: its pair tables as torch tensors on the batch's device (the layout
+    of sq_result_pairs_dev, gap-free coordinates), the host's copy of the sizes, and where the tables were formed."""
+    __slots__ = ("tables", "nstruct", "lengths", "source")
+
+    def __init__(self, tables, nstruct, lengths, source):
+        self.tables, self.nstruct, self.lengths, self.source = tables, nstruct, lengths, source
+
+
+def _upload_once(arrays, device):
+    """The numpy arrays as torch tensors on `device`, through ONE host-to-device copy (every array starts 8-byte aligned)."""
+    import torch
+    offs, total = [], 0
+    for a in arrays:
+        offs.append(total)
+        total += (a.nbytes + 7) & ~7
+    host = np.zeros(max(total, 8), np.uint8)
+    for a, o in zip(arrays, offs):
+        host[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    dev = torch.from_numpy(host).to(device)
+    return [dev[o:o + a.nbytes].view(getattr(torch, a.dtype.name)).reshape(a.shape) for a, o in zip(arrays, offs)]
+
+
+def _tensor_results(batches):
+    """fold_records(_tensors=True), fold_tensors' path: per batch [((its _TensorRun, record), None)].  The device tail's
+    results leave as tensors formed on the device (Batch.result_tensors); a batch whose tail ran on the host is converted
+    from its packed records (the same content; a Python loop over the records and their bracket levels on the host,
+    results.packed_pair_tables: the cost of such a batch's results, tens of microseconds per record) and uploaded once."""
+    res = []
+    for b in batches:
+        tables = b.result_tensors()
+        if tables is not None:
+            nstruct, lengths = b.result_counts()
+            run = _TensorRun(tables, nstruct, lengths, "device")
+        else:
+            host, nstruct, lengths = packed_pair_tables(*b.pack_all())
+            run = _TensorRun(dict(zip(_TABLES, _upload_once([host[k] for k in _TABLES], b.device))), nstruct, lengths, "host")
+        res.append([((run, k), None) for k in range(b.nseq)])
+    return res
+
+
+def _join_runs(runs):
+    """The tables of consecutive batches as one set: concatenated, the offsets rebased."""
+    import torch
+    if len(runs) == 1:
+        out = dict(runs[0].tables)
+    else:
+        out = {k: torch.cat([r.tables[k] for r in runs]) for k in ("partner", "scores", "pset_mask", "metrics")}
+        for key in ("row_off", "cell_off"):
+            parts, base = [], 0
+            for q, r in enumerate(runs):
+                t = r.tables[key]
+                parts.append((t if q == len(runs) - 1 else t[:-1]) + base)
+                base += int(r.nstruct.sum()) if key == "row_off" else int(((1 + r.nstruct) * r.lengths).sum())
+            out[key] = torch.cat(parts)
+    out["nstruct"] = np.concatenate([r.nstruct for r in runs])
+    out["lengths"] = np.concatenate([r.lengths for r in runs])
+    sources = {r.source for r in runs}
+    out["source"] = sources.pop() if len(sources) == 1 else "mixed"
+    return out
+
+
 def _tuple_results(batches):
     """fold_records: per batch [(SQRNdbnseq tuple, reference scores or None)]."""
     return [b.results_all() for b in batches]
@@ -129,6 +194,33 @@ class HipEngine:
         the payload ranks exchange (parallel.py).  `unpack_result(Prepared(...), blob)` decodes one on any rank."""
         return self.fold_records(records, _packed=True, **opts)
 
+    def fold_tensors(self, records, **opts):
+        """Like fold_records, but the results stay on the device as data: dict of torch tensors partner int32[cells],
+        scores float64[rows, 3], pset_mask int64[rows], metrics float64[records, 16], row_off / cell_off int64[records + 1]
+        in the layout of sq_result_pairs_dev (include/squarna_hip.h; gap-free coordinates), the host arrays nstruct and
+        lengths (int64 per record), and source: "device" when the ranking tail of every batch ran on the device, "host"
+        when none did (rankbydiff, forced hardrest pairs, conslim > 1, > 4,096 final structures: converted from the packed
+        records), "mixed" otherwise.  `keep` as for fold_records."""
+        import torch
+        if not records:
+            raise ValueError("fold_tensors needs at least one record")
+        kept = self.last_ref_scores                                  # (the known structures' scores are in the metrics table)
+        out = self.fold_records(records, _tensors=True, **opts)
+        self.last_ref_scores = kept
+        # every record carries (the tables of its batch, its place in them): the batches must cover the records in order,
+        # each whole -- what the sub-batch planner hands out; anything else would join the tables in another order
+        runs, at = [], 0
+        for run, k in out:
+            if not runs or runs[-1] is not run:
+                assert not runs or at == len(runs[-1].nstruct), "a batch's records are not consecutive"
+                runs.append(run)
+                at = 0
+            assert k == at, "a batch's records are not in order"
+            at += 1
+        assert at == len(runs[-1].nstruct), "a batch's records are not consecutive"
+        with torch.cuda.device(runs[0].tables["partner"].device):
+            return _join_runs(runs)
+
     def _fold_records(self, records, **opts):
         """`keep`: only the first `keep` structures of every record are fetched (Predict prints outplim of them)."""
         poollim = opts.get("poollim", 1000)
@@ -161,7 +253,7 @@ class HipEngine:
         # for the 500-vertex Edmonds graphs of its records however few they are.  Off by default.
         # Not the rows weighted by ONE device matrix: they share that tensor on the caller's stream.
         lanes = switches.engine_sublanes()
-        if direct or sum(dense) > 0 or opts.get("_blocks"):
+        if direct or sum(dense) > 0 or opts.get("_blocks") or opts.get("_tensors"):
             lanes = 1
         mkey = (tuple(tuple(sorted((k, str(v)) for k, v in ps.items())) for ps in records[0][4]),       # (the paramsets by content: an id() is reused)
                 int(opts.get("poollim", 1000)), max(len(r[0]) for r in records) // 64)
@@ -207,6 +299,7 @@ class HipEngine:
         opts = dict(opts)
         opts.pop("_packed", None)
         opts.pop("_blocks", None)
+        opts.pop("_tensors", None)
         interchainonly = opts.pop("interchainonly", False)
         keep = opts.pop("keep", None)
         M, B = opts.pop("M", 1.8), opts.pop("B", -0.6)
@@ -308,7 +401,7 @@ class HipEngine:
     def _fold_groups(self, groups, hints, opts, info=None, inflight=1):
         """Folds every group of records as one batch, all of them at the same time; ([results], [reference scores]) per
         group."""
-        groups, hints, back = _cut_in_two_lanes(groups, hints)
+        groups, hints, back = _cut_in_two_lanes(groups, hints, bool(opts.get("_tensors")))
         batches = self._fold_with_retry(groups, hints, opts, inflight)
         try:
             driver, peak = max(b.fold_driver for b in batches), batches[0].fold_peak_structs
@@ -320,6 +413,8 @@ class HipEngine:
                 res = _packed_results(batches)
             elif opts.get("_blocks"):
                 res = _block_results(batches, groups, opts["_blocks"])
+            elif opts.get("_tensors"):
+                res = _tensor_results(batches)
             else:
                 res = _tuple_results(batches)
         finally:

@@ -1,0 +1,369 @@
+"""``Fold``: bulk prediction that returns data instead of text.
+
+``Predict`` prints the reference's blocks and ``SQRNdbnseq`` returns one record's tuple; ``Fold`` takes the same inputs and
+prediction keywords as ``Predict`` and returns a :class:`FoldResult`: pair tables, scores, paramset masks and metrics of
+every record as torch tensors.  With the GPU engine the tables are formed by a kernel from the ranking tail's scratch
+(``sq_result_pairs_dev``) and never leave the device; an engine without ``fold_tensors`` (the tests' CPU engine) gets the
+same object built on the CPU from its ``fold_records`` tuples.  ``Fold`` prints nothing.
+"""
+import contextlib
+import io
+import os
+
+import numpy as np
+
+from . import api as _api
+from . import engine as _engine
+from .engine import _TABLES
+from .config import ParseConfig, DATA_DIR
+from .core import resolve_priority
+from .dbn import DBNToPairs, PairsToDBN, GAPS, SEPS, gap_mask
+from .inputs import ParseInput
+
+
+
+def _seg_copy(torch, dst, dst_start, src, src_start, seg_len, colmap=None, map_start=None):
+    """dst[dst_start[s] + t] = src[src_start[s] + t] for every segment s and t < seg_len[s], as torch index operations on
+    the tensors' device (the per-segment numbers are host int64 arrays, uploaded once).  With colmap (a device tensor)
+    and map_start, segment s is a row of partners that moves into other coordinates: entry t goes to column
+    colmap[map_start[s] + t] and a partner v >= 0 becomes colmap[map_start[s] + v]."""
+    total = int(seg_len.sum())
+    if not total:
+        return
+    dev = src.device
+    cum = np.zeros(len(seg_len), np.int64)
+    np.cumsum(seg_len[:-1], out=cum[1:])
+    cols = [dst_start, src_start - cum, cum, seg_len] + ([map_start] if colmap is not None else [])
+    meta = torch.from_numpy(np.stack(cols)).to(dev)
+    seg = torch.repeat_interleave(torch.arange(len(seg_len), device=dev), meta[3], output_size=total)
+    flat = torch.arange(total, device=dev)
+    val = src[flat + meta[1][seg]]
+    t = flat - meta[2][seg]
+    if colmap is None:
+        dst[meta[0][seg] + t] = val
+        return
+    base = meta[4][seg]
+    moved = colmap[base + val.clamp(min=0).long()]
+    dst[meta[0][seg] + colmap[base + t]] = torch.where(val >= 0, moved, torch.full_like(moved, -1)).to(dst.dtype)
+
+
+def _offsets(nstruct, lengths):
+    """(row_off, cell_off) of the tables' layout, int64[R + 1] each."""
+    row_off, cell_off = np.zeros(len(nstruct) + 1, np.int64), np.zeros(len(nstruct) + 1, np.int64)
+    np.cumsum(nstruct, out=row_off[1:])
+    np.cumsum((1 + nstruct) * lengths, out=cell_off[1:])
+    return row_off, cell_off
+
+
+class FoldResult:
+    """Predictions of ``Fold`` for R records.
+
+    Host lists: ``names``, ``sequences`` (as given), ``paramset_names`` (per record: the names its mask bits stand for).
+    Torch tensors (``device``: where they live): ``lengths`` and ``nstruct`` int64[R]; ``row_off`` / ``cell_off``
+    int64[R + 1]; ``partner`` int32[cells] -- record r has 1 + nstruct[r] rows of lengths[r] entries from
+    cell_off[r] on, row 0 the consensus, rows 1.. the structures in rank order, entry i the 0-based partner of position i
+    or -1; ``scores`` float64[rows, 3] (total, structure, reactivity) and ``pset_mask`` int64[rows] (bit p: paramset p
+    produced the structure; the bit pattern of the library's uint64) for the structure rows, record r from row_off[r] on;
+    ``metrics`` float64[R, 16]: TP FP FN FS PR RC of the consensus, the same + rank of the best of the top structures, the
+    known structure's three scores (NaN without one).  ``source``: "device", "host" or "mixed" -- where the tables
+    were formed (HipEngine.fold_tensors).
+
+    Positions count the sequence AS GIVEN: gap columns are -1 and partners point at input columns, so ``dbn(r, k)`` is the
+    string ``SQRNdbnseq`` returns."""
+
+    def __init__(self, names, sequences, paramset_names, tables, nstruct, lengths, source):
+        import torch
+        self.names, self.sequences, self.paramset_names, self.source = names, sequences, paramset_names, source
+        self.partner, self.scores, self.pset_mask, self.metrics, self.row_off, self.cell_off = (tables[k] for k in _TABLES)
+        # the host's copy of the sizes: the helpers below index with it, no device round trip
+        self._nstruct, self._lengths = np.asarray(nstruct, np.int64), np.asarray(lengths, np.int64)
+        self._row_off, self._cell_off = _offsets(self._nstruct, self._lengths)
+        self.lengths, self.nstruct = (torch.from_numpy(a).to(self.partner.device) for a in (self._lengths, self._nstruct))
+
+    def __len__(self):
+        return len(self.names)
+
+    @property
+    def device(self):
+        return self.partner.device
+
+    def cpu(self):
+        """The same result with every tensor in host memory."""
+        tables = {k: getattr(self, k).cpu() for k in _TABLES}
+        return FoldResult(self.names, self.sequences, self.paramset_names, tables, self._nstruct, self._lengths, self.source)
+
+    def _row(self, r, k):
+        """Row k of record r (0: the consensus) as a host int32 array."""
+        if not 0 <= k <= self._nstruct[r]:
+            raise IndexError("record %d has %d structures" % (r, self._nstruct[r]))
+        n, o = int(self._lengths[r]), int(self._cell_off[r])
+        return self.partner[o + k * n:o + (k + 1) * n].cpu().numpy()
+
+    def pairs(self, r, k):
+        """Sorted (i, j) pairs, i < j, of structure k (0-based, rank order) of record r."""
+        row = self._row(r, k + 1)
+        i = np.flatnonzero(row > np.arange(len(row)))
+        return list(zip(i.tolist(), row[i].tolist()))
+
+    def _dbn(self, r, row):
+        seq = self.sequences[r]
+        i = np.flatnonzero(row > np.arange(len(row)))
+        dbn = PairsToDBN(list(zip(i.tolist(), row[i].tolist())), len(seq))
+        return ''.join(seq[q] if seq[q] in SEPS else ch for q, ch in enumerate(dbn)) if any(ch in SEPS for ch in seq) else dbn
+
+    def dbn(self, r, k):
+        """Dot-bracket string of structure k of record r, as SQRNdbnseq returns it."""
+        return self._dbn(r, self._row(r, k + 1))
+
+    def consensus(self, r):
+        """Dot-bracket string of record r's consensus."""
+        return self._dbn(r, self._row(r, 0))
+
+    def paramsets(self, r, k):
+        """Names of the paramsets that produced structure k of record r."""
+        if not 0 <= k < self._nstruct[r]:
+            raise IndexError("record %d has %d structures" % (r, self._nstruct[r]))
+        m = int(self.pset_mask[int(self._row_off[r]) + k]) & 0xFFFFFFFFFFFFFFFF
+        names = self.paramset_names[r]
+        return [names[p] for p in range(len(names)) if (m >> p) & 1]
+
+    def to_padded(self, k=None):
+        """int32[R, K, Lmax]: the first K structures (default: the most any record has) of every record, -1 where a
+        record is shorter or has fewer; formed on the tensors' device."""
+        import torch
+        R = len(self.names)
+        K = int(self._nstruct.max(initial=0)) if k is None else int(k)
+        Lmax = int(self._lengths.max(initial=0))
+        out = torch.full((R, K, Lmax), -1, dtype=torch.int32, device=self.device)
+        take = np.minimum(self._nstruct, K)
+        rec = np.repeat(np.arange(R), take)
+        j = np.arange(len(rec)) - np.repeat(np.cumsum(take) - take, take)
+        _seg_copy(torch, out.view(-1), (rec * K + j) * Lmax, self.partner, self._cell_off[rec] + (1 + j) * self._lengths[rec],
+                  self._lengths[rec])
+        return out
+
+    def contact_map(self, r, k):
+        """bool[L, L] of structure k of record r: True where i and j pair (symmetric), on the tensors' device."""
+        import torch
+        if not 0 <= k < self._nstruct[r]:
+            raise IndexError("record %d has %d structures" % (r, self._nstruct[r]))
+        n, o = int(self._lengths[r]), int(self._cell_off[r])
+        row = self.partner[o + (k + 1) * n:o + (k + 2) * n].long()
+        return row[:, None] == torch.arange(n, device=self.device)[None, :]
+
+
+def _oracle_tables(results, seqs, keep):
+    """The tables of an engine's fold_records tuples, on the CPU: the strings are in input coordinates already."""
+    import torch
+    partner, scores, masks, nstruct = [], [], [], []
+    metrics = np.full((len(results), 16), np.nan)
+
+    def row(dbn, n):
+        p = np.full(n, -1, np.int32)
+        for v, w in DBNToPairs(dbn):
+            p[v], p[w] = w, v
+        return p
+    for r, ((cons, preds, cm, bm), seq, ref) in enumerate(results):
+        preds = preds[:keep]
+        nstruct.append(len(preds))
+        partner.append(row(cons, len(seq)))
+        for dbn, sc, ids in preds:
+            partner.append(row(dbn, len(seq)))
+            scores.append([float(x) for x in sc])
+            masks.append(sum(1 << p for p in ids))
+        if ref is not None:
+            metrics[r, :6], metrics[r, 6:13], metrics[r, 13:16] = cm, bm, ref
+    tables = dict(partner=torch.from_numpy(np.concatenate(partner)),
+                  scores=torch.from_numpy(np.array(scores, np.float64).reshape(-1, 3)),
+                  pset_mask=torch.from_numpy(np.array(masks, np.uint64).astype(np.int64)),
+                  metrics=torch.from_numpy(metrics))
+    nstruct, lengths = np.array(nstruct, np.int64), np.array([len(s) for s in seqs], np.int64)
+    tables["row_off"], tables["cell_off"] = (torch.from_numpy(a) for a in _offsets(nstruct, lengths))
+    return tables, nstruct, lengths
+
+
+def _join(parts, seqs):
+    """(tables, nstruct, lengths) in input order and input coordinates from the engine calls' results.  parts: (tables,
+    nstruct, lengths, records' places in the input, whether the coordinates are gap-free)."""
+    import torch
+    R = len(seqs)
+    if len(parts) == 1 and (not parts[0][4] or not any(g in s for s in seqs for g in GAPS)):
+        tables, ns, ln = parts[0][:3]                                # one call, no gap column: the kernel's output as it is
+        return {k: tables[k] for k in _TABLES}, ns, ln
+    nstruct, short, out_len = np.zeros(R, np.int64), np.zeros(R, np.int64), np.array([len(s) for s in seqs], np.int64)
+    for _, ns, ln, idx, _ in parts:
+        nstruct[idx], short[idx] = ns, ln
+    row_off, cell_off = _offsets(nstruct, out_len)
+    dev = parts[0][0]["partner"].device
+    partner = torch.full((int(cell_off[-1]),), -1, dtype=torch.int32, device=dev)
+    scores = torch.empty((int(row_off[-1]), 3), dtype=torch.float64, device=dev)
+    masks = torch.empty(int(row_off[-1]), dtype=torch.int64, device=dev)
+    metrics = torch.empty((R, 16), dtype=torch.float64, device=dev)
+    for tables, ns, ln, idx, gapfree in parts:
+        idx = np.asarray(idx, np.int64)
+        rows = 1 + ns
+        rec = np.repeat(np.arange(len(idx)), rows)                   # one segment per row of partners
+        j = np.arange(len(rec)) - np.repeat(np.cumsum(rows) - rows, rows)
+        src_cell = np.zeros(len(idx) + 1, np.int64)
+        np.cumsum(rows * ln, out=src_cell[1:])
+        colmap = map_start = None
+        if gapfree and any(short[k] != out_len[k] for k in idx):
+            # where every gap-free position of the part's records lies in its input sequence
+            pos = np.zeros(len(idx) + 1, np.int64)
+            np.cumsum(ln, out=pos[1:])
+            cm = np.arange(int(pos[-1]), dtype=np.int64) - np.repeat(pos[:-1], ln)
+            for q, k in enumerate(idx):
+                if short[k] != out_len[k]:
+                    cm[pos[q]:pos[q + 1]] = np.flatnonzero(~gap_mask(seqs[k]))
+            colmap, map_start = torch.from_numpy(cm).to(dev), pos[rec]
+        _seg_copy(torch, partner, cell_off[idx][rec] + j * out_len[idx][rec], tables["partner"], src_cell[rec] + j * ln[rec], ln[rec],
+                  colmap, map_start)
+        first = np.cumsum(ns) - ns                                   # the part's structure rows, record after record
+        dst = torch.from_numpy(np.repeat(row_off[idx] - first, ns) + np.arange(int(ns.sum()))).to(dev)
+        scores[dst], masks[dst] = tables["scores"], tables["pset_mask"]
+        metrics[torch.from_numpy(idx).to(dev)] = tables["metrics"]
+    return dict(partner=partner, scores=scores, pset_mask=masks, metrics=metrics, row_off=torch.from_numpy(row_off).to(dev),
+                cell_off=torch.from_numpy(cell_off).to(dev)), nstruct, out_len
+
+
+def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, inputformat="qtrf", maxstemnum=None,
+         algorithms='', rankby="r", hardrest=False, interchainonly=False, toplim=5, outplim=None, conslim=1, poollim=1000,
+         levellimit=None, ignorewarn=False, HOME_DIR=None, priority=None, M=1.8, B=-0.6, records=None,
+         alignment=False, evalonly=False, entropy=False, rfam=False, g4=False, rbp=False,
+         i=None, ff=None, c=None, config=None, s=None, seq=None, algo=None, algorithm=None, rb=None, ll=None, levlim=None,
+         tl=None, ol=None, cl=None, pl=None, pr=None, msn=None, hr=None, ico=None, iw=None, ignore=None, a=None, ali=None,
+         eo=None, inputrestr=None):
+    """Predict the structures of every input record and return them as a :class:`FoldResult`.
+
+    The inputs (``inputfile`` / ``inputseq``), the prediction keywords, their defaults, synonyms, validation messages and the
+    choice of configuration by length when no ``configfile`` is given are ``Predict``'s.  ``records`` gives the input directly
+    instead: sequences, or (name, sequence, reactivities, restraints, reference) tuples with None for what a record lacks.
+    ``outplim`` (default: ``toplim``) bounds the structures kept per record.  Alignment mode, ``evalonly``, ``entropy`` and
+    the ``rfam`` / ``g4`` / ``rbp`` restraint searches belong to ``Predict`` and raise ValueError here."""
+    def pick(cur, *alts):
+        for alt in alts:
+            if alt is not None:
+                cur = alt
+        return cur
+    inputfile = pick(inputfile, i); fileformat = pick(fileformat, ff)
+    configfile = pick(configfile, config, c); inputseq = pick(inputseq, seq, s)
+    algorithms = pick(algorithms, algorithm, algo); rankby = pick(rankby, rb)
+    levellimit = pick(levellimit, levlim, ll); toplim = pick(toplim, tl); outplim = pick(outplim, ol)
+    conslim = pick(conslim, cl); poollim = pick(poollim, pl); priority = pick(priority, pr)
+    maxstemnum = pick(maxstemnum, msn); hardrest = pick(hardrest, hr); interchainonly = pick(interchainonly, ico)
+    ignorewarn = pick(ignorewarn, ignore, iw)
+    for flag, what in ((pick(alignment, ali, a), "alignment mode"), (pick(evalonly, eo), "evalonly"), (entropy, "entropy"),
+                       (rfam, "rfam"), (g4, "g4"), (rbp, "rbp")):
+        if flag:
+            raise ValueError("Fold does not cover {}: use Predict".format(what))
+
+    if HOME_DIR is None:
+        HOME_DIR = DATA_DIR
+    if inputfile != None and not os.path.exists(inputfile) and os.path.exists(os.path.join(HOME_DIR, inputfile)):
+        inputfile = os.path.join(HOME_DIR, inputfile)
+
+    # ---- validation: Predict's checks of the keywords both take, same messages (SQUARNA.py:677-808)
+    assert records is not None or os.path.exists(str(inputfile)) or inputseq, "Input file does not exist."
+    assert fileformat in {'unknown', 'fasta', 'default', 'stockholm', 'clustal'}, \
+        "Wrong fileformat, choose one of these: default,fasta,stockholm,clustal"
+    configfile, configfileset, priority = _api._find_config(configfile, HOME_DIR, priority)
+    assert ''.join(sorted(inputformat.replace('x', ''))) in {"q", "fq", "qr", "qt", "qrt", "fqr", "fqt", "fqrt"}, \
+        'Inappropriate inputformat value (subset of "fqrtx" with "q" being mandatory): {}'.format(inputformat)
+
+    if maxstemnum is not None:
+        maxstemnum = _api._as_int(maxstemnum, "maxstemnum", lambda x: x >= 0, "non-negative integer")
+    try:
+        M = float(M)
+    except Exception:
+        raise ValueError("Inappropriate M value (float): {}".format(M))
+    try:
+        B = float(B)
+    except Exception:
+        raise ValueError("Inappropriate B value (float): {}".format(B))
+    try:
+        algos = set(algorithms.upper())
+        assert algos <= {'E', 'G', 'H', 'N'}
+    except Exception:
+        raise ValueError('Inappropriate algorithm value (should be subset of "eghn"): {}'.format(algorithms))
+    assert rankby in {"r", "s", "rs", "dr", "ds", "drs"}, 'Inappropriate rankby value (r/s/rs/dr/ds/drs): {}'.format(rankby)
+    if outplim is not None:
+        outplim = _api._as_int(outplim, "outplim", lambda x: x > 0, "positive integer")
+    toplim = _api._as_int(toplim, "toplim", lambda x: x > 0, "positive integer")
+    if outplim is None:
+        outplim = toplim
+    conslim = _api._as_int(conslim, "conslim", lambda x: x > 0, "positive integer")
+    poollim = _api._as_int(poollim, "poollim", lambda x: x > 0, "positive integer")
+    if levellimit is not None:
+        try:
+            levellimit = int(float(levellimit))
+        except Exception:
+            raise ValueError("Inappropriate levellimit value (integer): {}".format(levellimit))
+    rankbydiff, rankby = _api._rank_keys(rankby)
+
+    configs = [ParseConfig(configfile)]
+    if not configfileset:                                        # autoconfig, SQUARNA.py:868-878
+        configs += [ParseConfig(os.path.join(HOME_DIR, "500.conf")), ParseConfig(os.path.join(HOME_DIR, "1000.conf"))]
+    if maxstemnum is not None:
+        for _, group in configs:
+            for ps in group:
+                ps['maxstemnum'] = maxstemnum
+
+    def config_for(sequence):
+        if configfileset or len(sequence) < 500:
+            return configs[0]
+        return configs[2] if len(sequence) >= 1000 else configs[1]
+
+    if records is not None:
+        inputs = [(">record{}".format(k + 1), rec, None, None, None) if isinstance(rec, str) else tuple(rec)
+                  for k, rec in enumerate(records)]
+        assert all(len(rec) == 5 for rec in inputs), "records: sequences or (name, sequence, reactivities, restraints, reference)"
+    else:
+        with contextlib.redirect_stdout(io.StringIO()):          # (the parser announces a guessed file format)
+            inputs = list(ParseInput(inputseq, inputfile, inputformat, fmt=fileformat, ignore=ignorewarn,
+                                     inputrestr=inputrestr, M=M, B=B)[0])
+    assert inputs, "No input records."
+
+    eng = _engine.get_engine()
+    keep = max(int(outplim), 1)
+    common = dict(conslim=conslim, toplim=toplim, hardrest=hardrest, rankbydiff=rankbydiff, rankby=rankby,
+                  interchainonly=interchainonly, poollim=poollim, algos=algos, levellimit=levellimit, M=M, B=B, keep=keep)
+    seqs = [rec[1] for rec in inputs]
+    psnames = [config_for(sq)[0] for sq in seqs]
+    parts = []
+
+    def flush(batch):
+        # records with different priority index sets cannot share one fold call (as in Predict)
+        groups = {}
+        for k in batch:
+            groups.setdefault(tuple(sorted(resolve_priority(priority, psnames[k]))), []).append(k)
+        for prio, idx in groups.items():
+            recs = [(inputs[k][1], inputs[k][2], inputs[k][3], inputs[k][4], config_for(seqs[k])[1], None) for k in idx]
+            if hasattr(eng, "fold_tensors"):
+                t = eng.fold_tensors(recs, priority=set(prio), **common)
+                parts.append((t, t["nstruct"], t["lengths"], idx, True, t["source"]))
+            else:
+                res = eng.fold_records(recs, priority=set(prio), **common)
+                refsc = getattr(eng, "last_ref_scores", None) or [None] * len(idx)
+                full = [(r, seqs[k], (rs if rs is not None else _ref_scores(inputs[k])) if inputs[k][4] else None)
+                        for r, k, rs in zip(res, idx, refsc)]
+                parts.append(_oracle_tables(full, [seqs[k] for k in idx], keep) + (idx, False, "host"))
+
+    batch, cells = [], 0
+    for k, sq in enumerate(seqs):                                # Predict's batches (api._predict_records)
+        batch.append(k)
+        cells += len(sq) * len(sq) * len(config_for(sq)[1])
+        if len(batch) >= _api.BATCH_RECORDS or cells >= _api.BATCH_CELLS:
+            flush(batch)
+            batch, cells = [], 0
+    if batch:
+        flush(batch)
+    sources = {p[5] for p in parts}
+    tables, nstruct, lengths = _join([p[:5] for p in parts], seqs)
+    return FoldResult([rec[0] for rec in inputs], seqs, psnames, tables, nstruct, lengths,
+                      sources.pop() if len(sources) == 1 else "mixed")
+
+
+def _ref_scores(rec):
+    """ScoreStruct of a record's known structure for an engine that does not report it (ReferenceScores, SQRNdbnseq.py:958-970)."""
+    from .core import ReferenceScores
+    return ReferenceScores(rec[1], rec[4], rec[2])

@@ -96,3 +96,47 @@ def _metrics(m):
     pr = float(m[4]) if tp + fp else 1
     rc = float(m[5]) if tp + fn else 1
     return [tp, fp, fn, fs, pr, rc]
+
+
+def _level_partners(lev):
+    """Partner arrays of bracket-level rows (int16[rows, n]: +L opens, -L closes a pair of level L) as int32[rows, n],
+    -1 unpaired.  The brackets of one level nest, so an opener and its closer are neighbours once the brackets of a row
+    are ordered by (depth, position): array code, no per-position loop."""
+    out = np.full(lev.shape, -1, np.int32)
+    for L in range(1, int(np.abs(lev).max(initial=0)) + 1):
+        s = (lev == L).astype(np.int32) - (lev == -L).astype(np.int32)
+        rr, pp = np.nonzero(s)
+        if not len(rr):
+            continue
+        depth = np.cumsum(s, axis=1)[rr, pp] + (s[rr, pp] < 0)       # an opener and its closer: the same number
+        order = np.lexsort((pp, depth, rr))
+        a, b = order[0::2], order[1::2]
+        out[rr[a], pp[a]] = pp[b]
+        out[rr[b], pp[b]] = pp[a]
+    return out
+
+
+def packed_pair_tables(buf, off):
+    """The packed records of a batch (Batch.pack_all) in the layout of sq_result_pairs_dev (include/squarna_hip.h), as
+    numpy arrays: what a batch whose ranking tail ran on the host hands to HipEngine.fold_tensors.  A Python loop over the
+    records (array code per record and bracket level): the fallback's cost grows with the number of records, unlike the
+    device path's."""
+    nseq = len(off) - 1
+    raw = bytes(buf)
+    nstruct, lengths = np.zeros(nseq, np.int64), np.zeros(nseq, np.int64)
+    partner, scores, masks = [], [], []
+    metrics = np.zeros((nseq, 16), np.float64)
+    for k in range(nseq):
+        base = int(off[k])
+        ns, n, _, _ = _HDR.unpack_from(raw, base)
+        nstruct[k], lengths[k] = ns, n
+        metrics[k] = _MET.unpack_from(raw, base + 32)
+        scores.append(np.frombuffer(raw, '<f8', 3 * ns, base + 160))
+        masks.append(np.frombuffer(raw, '<i8', ns, base + 160 + 24 * ns))
+        partner.append(_level_partners(np.frombuffer(raw, '<i2', (ns + 1) * n, base + 160 + 32 * ns).reshape(ns + 1, n)).reshape(-1))
+    cat = lambda parts, dt: np.concatenate(parts).astype(dt, copy=False) if parts else np.zeros(0, dt)
+    row_off, cell_off = np.zeros(nseq + 1, np.int64), np.zeros(nseq + 1, np.int64)
+    np.cumsum(nstruct, out=row_off[1:])
+    np.cumsum((1 + nstruct) * lengths, out=cell_off[1:])
+    return dict(partner=cat(partner, np.int32), scores=cat(scores, np.float64).reshape(-1, 3), pset_mask=cat(masks, np.int64),
+                metrics=metrics, row_off=row_off, cell_off=cell_off), nstruct, lengths

@@ -428,6 +428,31 @@ SQ_API int sq_align_accumulate(sq_batch *b, int32_t njob, const int32_t *job_ids
 SQ_API int sq_colmatrix_select(const double *d_matrix, int32_t L, double threshold, int32_t minspan,
                                int64_t *d_idx, double *d_val, int64_t cap, uint64_t *d_count, void *hip_stream);
 
+/* ---- alignment consensus on the device (SQRNdbnali.py:121-192, 271-304) -------------------------------
+ * sq_align_pair_count -- Consensus' dict (:281-284) from the pair tables of a fold.  d_partner / d_cell_off: the layout of
+ * sq_result_pairs_dev (gap-free coordinates); row 0 of each of the nrec records -- its consensus -- is read.  d_col_off
+ * int32[nrec + 1] / d_cols: the records' gap maps in sq_align_accumulate's form, in DEVICE memory: d_cols[d_col_off[r] + p] is
+ * the alignment column of position p of record r, and d_col_off[r + 1] - d_col_off[r] the record's length.  Every pair
+ * (i, j), i < j, becomes the column pair (v, w); for every distinct one, count = the number of records that hold it and
+ * first = the smallest index of such a record.  The distinct pairs with count >= threshold (>= 1) are written, unordered, as
+ * d_flat[k] = v * L + w, d_count[k], d_first[k]; d_out[0] = their number (may exceed cap: then only the first cap were
+ * stored, as for sq_colmatrix_select), d_out[1] = 0, or 2 when a table entry pointed outside its record or the L columns
+ * (such an entry is not counted).  d_scratch: sq_align_pair_count_scratch(L) bytes (two dense int32 L x L tables), set here.
+ * sq_first_fit_dev -- the sequential pass of sq_align_first_fit / Consensus (:285-295) over d_flat[n], candidates v * L + w
+ * given in rank order: a candidate with v < w and w - v >= minspan is taken iff both of its columns are still free.
+ * d_partner int32[L]: the partner of every column, -1 where free.  d_info int32[4]: status (0, or 1: more than L / 2 + 1
+ * rounds -- cannot happen, the loop is bounded by it; the result is then incomplete), the rounds used, the pairs taken,
+ * candidates left live (0 with status 0).  One launch of one workgroup (rounds: csrc/sq_firstfit.h).  d_scratch:
+ * sq_first_fit_scratch(n, L) bytes.
+ * Both are asynchronous on hip_stream and allocate nothing; 0, or -1 (bad argument, scratch too small: nothing enqueued). */
+SQ_API size_t sq_align_pair_count_scratch(int32_t L);
+SQ_API int sq_align_pair_count(const int32_t *d_partner, const int64_t *d_cell_off, const int32_t *d_col_off, const int32_t *d_cols,
+                               int32_t nrec, int32_t L, int32_t threshold, void *d_scratch, size_t scratch_bytes, int64_t *d_flat,
+                               int32_t *d_count, int32_t *d_first, int64_t cap, uint64_t *d_out, void *hip_stream);
+SQ_API size_t sq_first_fit_scratch(int64_t n, int32_t L);
+SQ_API int sq_first_fit_dev(const int64_t *d_flat, int64_t n, int32_t L, int32_t minspan, int32_t *d_partner, void *d_scratch,
+                            size_t scratch_bytes, int32_t *d_info, void *hip_stream);
+
 /* ---- measurement ------------------------------------------------------------
  * Kernel ids: 0 fill, 1 state, 2 stem_scan, 3 stem_score (+ select), 4 Edmonds, 5 Hungarian,
  * 6 Nussinov.  When enabled, every launch is bracketed by hipEvents on the stream it runs on

@@ -16,6 +16,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 from .config import ParseConfig  # noqa: F401,E402
 from .api import Predict, Main  # noqa: F401,E402
 from .fold import Fold, FoldResult  # noqa: F401,E402
+from .fold_align import FoldAlignment, AlignmentResult  # noqa: F401,E402
 from .core import (BPMatrix, AnnotateStems, OptimalStems, RunAlgo, Edmonds, Hungarian, Nussinov,  # noqa: F401,E402
                    SQRNdbnseq, RunSQRNdbnseq, ScoreStruct, ReferenceScores)
 
@@ -26,5 +27,5 @@ def BuildRfam(*args, **kwargs):
     raise NotImplementedError("BuildRfam is out of scope of squarna_amd (see DESIGN.md)")
 
 
-__all__ = ["Predict", "Main", "Fold", "FoldResult", "BuildRfam", "ParseConfig", "BPMatrix", "AnnotateStems", "OptimalStems", "RunAlgo",
+__all__ = ["Predict", "Main", "Fold", "FoldResult", "FoldAlignment", "AlignmentResult", "BuildRfam", "ParseConfig", "BPMatrix", "AnnotateStems", "OptimalStems", "RunAlgo",
            "Edmonds", "Hungarian", "Nussinov", "SQRNdbnseq", "RunSQRNdbnseq"]

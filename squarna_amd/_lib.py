@@ -23,7 +23,8 @@ SYMBOLS = ["sq_version", "sq_last_error", "sq_last_capacity", "sq_batch_workspac
            "sq_align_accumulate", "sq_colmatrix_select", "sq_fold_concurrent", "sq_fold_concurrent_n", "sq_fold_driver", "sq_fold_paths", "sq_fold_peak_structs", "sq_result_limit",
            "sq_mwm_workspace_bytes", "sq_mwm", "sq_lsap_workspace_bytes", "sq_lsap",
            "sq_nussinov_workspace_bytes", "sq_nussinov", "sq_dbn_pairs", "sq_write_blocks", "sq_parse_default",
-           "sq_host_cache_trim", "sq_align_first_fit", "sq_result_pairs_size", "sq_result_pairs_dev"]
+           "sq_host_cache_trim", "sq_align_first_fit", "sq_result_pairs_size", "sq_result_pairs_dev",
+           "sq_align_pair_count_scratch", "sq_align_pair_count", "sq_first_fit_scratch", "sq_first_fit_dev"]
 
 BATCH_NO_FP32 = 1
 BATCH_POOL_LISTS = 2
@@ -160,6 +161,14 @@ def load():
     L.sq_align_accumulate.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.sq_colmatrix_select.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                       C.c_void_p, C.c_void_p]
+    L.sq_align_pair_count_scratch.restype = C.c_size_t
+    L.sq_align_pair_count_scratch.argtypes = [C.c_int32]
+    L.sq_align_pair_count.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                      C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.sq_first_fit_scratch.restype = C.c_size_t
+    L.sq_first_fit_scratch.argtypes = [C.c_int64, C.c_int32]
+    L.sq_first_fit_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                   C.c_void_p]
     L.sq_mwm_workspace_bytes.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
     L.sq_mwm.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                          C.c_void_p, C.c_size_t, C.c_void_p]

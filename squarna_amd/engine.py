@@ -511,9 +511,9 @@ class HipEngine:
             lo = hi
         return matrix
 
-    def matrix_cells(self, matrix, threshold, minspan=4, sort=True):
-        """(flat indices, values) of the upper cells >= threshold with span >= minspan of a device matrix,
-        sorted by flat index unless sort=False (MatrixToDBNs' candidates, SQRNdbnali.py:127-148)."""
+    def matrix_select(self, matrix, threshold, minspan=4):
+        """Device tensors (flat indices int64, values float64) of the upper cells >= threshold with span >= minspan of a
+        device matrix, unordered (sq_colmatrix_select); only the cells' number comes to the host."""
         import torch
         Lcols = int(matrix.shape[0])
         cap = 1 << 16
@@ -529,11 +529,72 @@ class HipEngine:
             if n <= cap:
                 break
             cap = n
-        idx, val = idx[:n].cpu().numpy(), val[:n].cpu().numpy()
+        return idx[:n], val[:n]
+
+    def matrix_cells(self, matrix, threshold, minspan=4, sort=True):
+        """(flat indices, values) of the upper cells >= threshold with span >= minspan of a device matrix,
+        sorted by flat index unless sort=False (MatrixToDBNs' candidates, SQRNdbnali.py:127-148)."""
+        idx, val = self.matrix_select(matrix, threshold, minspan)
+        idx, val = idx.cpu().numpy(), val.cpu().numpy()
         if not sort:
             return idx, val
         order = np.argsort(idx, kind="stable")
         return idx[order], val[order]
+
+    def first_fit(self, flat, Lcols, minspan=0):
+        """The greedy pass over ranked candidates on the device (sq_first_fit_dev): flat = int64 device tensor of cells
+        v * Lcols + w in rank order; a candidate of span >= minspan joins iff both of its columns are still free
+        (MatrixToDBNs' first structure SQRNdbnali.py:127-192 with minspan 4, Consensus :285-295 with none).  Returns
+        (partner int32[Lcols] on the device, -1 where free; info int32[4] on the device: status, rounds, pairs, live).
+        Enqueued on the current stream; nothing is waited for."""
+        import torch
+        flat = flat.contiguous()
+        assert flat.dtype == torch.int64 and flat.is_cuda and flat.dim() == 1
+        L = _lib.load()
+        n, dev = int(flat.numel()), flat.device
+        with torch.cuda.device(dev):
+            nbytes = int(L.sq_first_fit_scratch(n, int(Lcols)))
+            scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+            partner = torch.empty(int(Lcols), dtype=torch.int32, device=dev)
+            info = torch.empty(4, dtype=torch.int32, device=dev)
+            _lib.check(L.sq_first_fit_dev(C.c_void_p(flat.data_ptr() if n else None), n, int(Lcols), int(minspan),
+                                          C.c_void_p(partner.data_ptr()), C.c_void_p(scratch.data_ptr()), nbytes,
+                                          C.c_void_p(info.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return partner, info
+
+    def align_pair_count(self, partner, cell_off, gap_maps, Lcols, threshold=1):
+        """Consensus' dict on the device (sq_align_pair_count): partner / cell_off = the pair tables of fold_tensors (gap-free
+        coordinates), gap_maps = per record the int32 array of its positions' alignment columns.  Returns the device
+        tensors (flat int64 = v * Lcols + w, count int32, first int32) of the distinct column pairs that at least
+        `threshold` records' consensus rows hold, unordered; only their number comes to the host."""
+        import torch
+        L = _lib.load()
+        dev, nrec = partner.device, len(gap_maps)
+        col_off = np.zeros(nrec + 1, np.int32)
+        np.cumsum([len(g) for g in gap_maps], out=col_off[1:])
+        cols = np.concatenate(gap_maps).astype(np.int32) if nrec else np.zeros(0, np.int32)
+        assert int(cell_off.numel()) == nrec + 1
+        cap = max(int(col_off[-1]) // 2, 1)                          # (a record of n positions holds at most n / 2 pairs)
+        with torch.cuda.device(dev):
+            if not partner.numel():                                  # (every row all gaps: no table, no pair)
+                return tuple(torch.empty(0, dtype=dt, device=dev) for dt in (torch.int64, torch.int32, torch.int32))
+            d_off, d_cols = _upload_once([col_off, cols if len(cols) else np.zeros(1, np.int32)], dev)
+            nbytes = int(L.sq_align_pair_count_scratch(int(Lcols)))
+            scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+            flat = torch.empty(cap, dtype=torch.int64, device=dev)
+            count = torch.empty(cap, dtype=torch.int32, device=dev)
+            first = torch.empty(cap, dtype=torch.int32, device=dev)
+            out = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.check(L.sq_align_pair_count(C.c_void_p(partner.data_ptr()), C.c_void_p(cell_off.data_ptr()),
+                                             C.c_void_p(d_off.data_ptr()), C.c_void_p(d_cols.data_ptr()), nrec, int(Lcols),
+                                             int(threshold), C.c_void_p(scratch.data_ptr()), nbytes, C.c_void_p(flat.data_ptr()),
+                                             C.c_void_p(count.data_ptr()), C.c_void_p(first.data_ptr()), cap,
+                                             C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            n, status = out.tolist()
+        if status:
+            raise RuntimeError("sq_align_pair_count: a pair table entry lies outside its record or the %d columns" % Lcols)
+        assert n <= cap
+        return flat[:n], count[:n], first[:n]
 
     def entropy(self, record, interchainonly=False):
         """Mean row entropy of the stem matrix under the FIRST paramset, as a string

@@ -238,8 +238,9 @@ def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, i
     The inputs (``inputfile`` / ``inputseq``), the prediction keywords, their defaults, synonyms, validation messages and the
     choice of configuration by length when no ``configfile`` is given are ``Predict``'s.  ``records`` gives the input directly
     instead: sequences, or (name, sequence, reactivities, restraints, reference) tuples with None for what a record lacks.
-    ``outplim`` (default: ``toplim``) bounds the structures kept per record.  Alignment mode, ``evalonly``, ``entropy`` and
-    the ``rfam`` / ``g4`` / ``rbp`` restraint searches belong to ``Predict`` and raise ValueError here."""
+    ``outplim`` (default: ``toplim``) bounds the structures kept per record.  Alignment mode has a function of its own:
+    use ``FoldAlignment``.  ``evalonly``, ``entropy`` and the ``rfam`` / ``g4`` / ``rbp`` restraint searches belong to
+    ``Predict``.  All of these raise ValueError here."""
     def pick(cur, *alts):
         for alt in alts:
             if alt is not None:

@@ -87,7 +87,8 @@ typedef struct sq_batch_desc {
                                         ViennaRNA's base-pair probabilities; the fill applies scoremat *= term (bpp > 0)
                                         or scoremat += term (bpp < 0) (SQRNdbnseq.py:341-364).  A job takes either
                                         mul_score or bpp_term, not both.  NULL entry with bpp != 0: max(bppm) was 0,
-                                        the matrix stays as it is (:350,360).                                        */
+                                        the matrix stays as it is (:350,360).  Probabilities that are on the device
+                                        already: bpp_matrix_dev below, the term is then formed there.                */
     int32_t interchainonly;     /* SQRNdbnseq.py:264-271,301 */
     int32_t max_structs;        /* structures evaluated per round chunk (0 = default 4096); also the structure
                                    slots of the device-side pools / chained rounds: a fold whose pools outgrow
@@ -108,6 +109,19 @@ typedef struct sq_batch_desc {
     const int32_t *mul_cols;        /* [seq_off[nseq]] host: column of every position (same offsets as codes)   */
     const uint8_t *mul_shared;      /* [njobs] host                                                              */
     double mul_maxabs;              /* max |M| (an upper bound is enough: it only widens the scan's fp32 margin) */
+    /* Base-pair probabilities that already live on the device (a GPU predictor or partition function; one upload reused
+     * across paramsets and calls): per sequence ONE N x N row-major fp64 matrix `bppm`, values >= 0, in DEVICE memory.
+     * Every bpp != 0 job of such a sequence gets its term (bppm / max(bppm)) ** |bpp| formed on the device at
+     * sq_batch_create, where bpp_term's upload would have put it (same workspace bytes as a host bpp_term on those jobs):
+     * one kernel takes each matrix's maximum, one reads every element once and writes q = b / max (|bpp| == 1) or sqrt(q)
+     * (|bpp| == 0.5) to each job -- the IEEE operations numpy performs, so the bytes are those of a host-formed term.
+     * max == 0: the neutral term (1.0 multiplied, -0.0 added), the matrix stays as it is (:350,360).  Other exponents
+     * return -1: they take the host term (bpp_term), because the host libm's pow is the rule there.  Such a job has no
+     * bpp_term / mul_score / caller matrices / mul_shared (-4).  The kernels run on the batch's stream: the matrices must
+     * be complete there; they are not read after sq_batch_create returns and never written.  sq_batch_workspace_bytes
+     * only compares the entries with NULL.  Appended at the end: descriptors of earlier versions keep their layout. */
+    const double *const *bpp_matrix_dev;   /* [nseq] host array of DEVICE pointers; NULL entries allowed, array may be NULL   */
+    const int32_t *bpp_matrix_ld;          /* [nseq] host: row stride of each matrix in doubles (>= N); NULL: dense, ld = N */
 } sq_batch_desc;
 
 /* No fp32 score matrices in the workspace (4 N^2 bytes per job saved): everything except
@@ -455,8 +469,9 @@ SQ_API int sq_first_fit_dev(const int64_t *d_flat, int64_t n, int32_t L, int32_t
 
 /* ---- measurement ------------------------------------------------------------
  * Kernel ids: 0 fill, 1 state, 2 stem_scan, 3 stem_score (+ select), 4 Edmonds, 5 Hungarian,
- * 6 Nussinov.  When enabled, every launch is bracketed by hipEvents on the stream it runs on
- * (the matching kernels run on the batch's side streams). */
+ * 6 Nussinov, 9 the bpp terms formed at sq_batch_create from bpp_matrix_dev (both kernels; recorded whether profiling
+ * is enabled or not; alg_bytes = 8 N^2 (2 + bpp jobs) per sequence).  When enabled, every launch is bracketed by
+ * hipEvents on the stream it runs on (the matching kernels run on the batch's side streams). */
 SQ_API int sq_profile_enable(sq_batch *b, int32_t on);
 SQ_API int sq_profile_get(sq_batch *b, int32_t kernel, double *total_ms, int64_t *launches, double *alg_bytes);
 SQ_API int sq_profile_reset(sq_batch *b);

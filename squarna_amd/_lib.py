@@ -66,7 +66,9 @@ class BatchDesc(C.Structure):
                 ("mul_L", C.c_int32),
                 ("mul_cols", C.POINTER(C.c_int32)),
                 ("mul_shared", C.POINTER(C.c_uint8)),
-                ("mul_maxabs", C.c_double)]
+                ("mul_maxabs", C.c_double),
+                ("bpp_matrix_dev", C.POINTER(C.c_void_p)),
+                ("bpp_matrix_ld", C.POINTER(C.c_int32))]
 
 
 class Stem(C.Structure):

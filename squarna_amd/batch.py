@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .bpp import check_bpp_matrix
 from .dbn import DBNToPairs, encode_seq
 from .plan import workspace_size_class
 from .records import PackedRows
@@ -41,13 +42,19 @@ class Batch:
     """A device-resident batch of fold jobs (one per (record, paramset))."""
 
     def __init__(self, prepared, psets_per_record, interchainonly=False, ext=None, mul=None,
-                 max_structs=0, cand_per_nt=0, device=None, fp32=True, bpp=None, mul_shared=None, pool_lists=False):
+                 max_structs=0, cand_per_nt=0, device=None, fp32=True, bpp=None, mul_shared=None, pool_lists=False,
+                 bpp_dev=None):
         """fp32=False leaves the fp32 score matrices out of the workspace (4 N^2 bytes per job): everything
         but fill() works -- folding only needs the 1-bit-per-cell matrices.
         pool_lists=True: the batch will be folded with pools wider than one; with sequences of 257-1,024 nt the workspace
         then holds the pages of the lists a pool's structures hand to their children (SQ_BATCH_POOL_LISTS).
         mul_shared = (M, cols, maxabs): ONE L x L fp64 torch tensor on the GPU that weights every job of every record
-        (alignment step 2), cols[k] = the alignment columns of record k's gap-free positions, maxabs >= max |M|."""
+        (alignment step 2), cols[k] = the alignment columns of record k's gap-free positions, maxabs >= max |M|.
+        bpp_dev: per record a CUDA float64 N x N torch tensor of base-pair probabilities (values >= 0), or None: the terms of
+        the record's bpp != 0 jobs (|bpp| 0.5 or 1) are formed on the device at creation (sq_batch_desc.bpp_matrix_dev) instead
+        of being uploaded per job through `bpp`.  A tensor may be a view with a row stride >= N and unit column stride: it is
+        passed with its stride, not copied.  It must be complete on the current stream, is never written, and the Batch
+        keeps a reference until close()."""
         import torch
         L = _lib.load()
         if not torch.cuda.is_available():
@@ -65,7 +72,7 @@ class Batch:
             nseq = self._host_arrays(prepared)
         self._pool_lists = bool(pool_lists)
         self._job_lists(nseq, psets_per_record)
-        self._describe(interchainonly, ext, mul, max_structs, cand_per_nt, fp32, bpp, mul_shared)
+        self._describe(interchainonly, ext, mul, max_structs, cand_per_nt, fp32, bpp, mul_shared, bpp_dev)
         self._create_on_device(device)
 
     def _host_arrays(self, prepared):
@@ -139,7 +146,8 @@ class Batch:
         self.njobs = len(self.job_seq)
         self.nseq = nseq
 
-    def _describe(self, interchainonly=False, ext=None, mul=None, max_structs=0, cand_per_nt=0, fp32=True, bpp=None, mul_shared=None):
+    def _describe(self, interchainonly=False, ext=None, mul=None, max_structs=0, cand_per_nt=0, fp32=True, bpp=None, mul_shared=None,
+                  bpp_dev=None):
         """Fills self.desc (sq_batch_desc) from the host arrays and the job lists: no device work -- torch is touched only for
         mul_shared's matrix, which lives on the GPU."""
         nseq, njobs, ltot = self.nseq, self.njobs, int(self.seq_off[-1])
@@ -192,6 +200,22 @@ class Batch:
         if bpp is not None:                                          # per job: (bppm/max)**|bpp| or None (SQRNdbnseq.py:350-364)
             self._bpp = ptr_array(bpp)
             d.bpp_term = C.cast(self._bpp, C.POINTER(C.c_void_p))
+        self._bpp_dev = None
+        if bpp_dev is not None and any(m is not None for m in bpp_dev):   # per record: the probabilities themselves, on the device
+            if len(bpp_dev) != nseq:
+                raise ValueError("bpp_dev: %d matrices for %d records" % (len(bpp_dev), nseq))
+            self._bpp_dev = list(bpp_dev)                            # (kept until close(): the create's kernels read them)
+            self._bpp_ptr = (C.c_void_p * nseq)()
+            self._bpp_ld = np.zeros(max(nseq, 1), np.int32)
+            for k, m in enumerate(bpp_dev):
+                n = int(self.seq_off[k + 1] - self.seq_off[k])
+                self._bpp_ld[k] = n
+                if m is not None:
+                    check_bpp_matrix(m, n, "bpp_dev[%d]" % k)
+                    self._bpp_ptr[k] = m.data_ptr()
+                    self._bpp_ld[k] = int(m.stride(0)) if n > 1 else n
+            d.bpp_matrix_dev = C.cast(self._bpp_ptr, C.POINTER(C.c_void_p))
+            d.bpp_matrix_ld = _ptr(self._bpp_ld, C.POINTER(C.c_int32))
         d.interchainonly = int(bool(interchainonly))
         d.max_structs = int(max_structs)
         d.cand_per_nt = int(cand_per_nt)
@@ -225,6 +249,7 @@ class Batch:
             self.L.sq_batch_destroy(self.h)
             self.h = None
             self.workspace = None
+            self._bpp_dev = None
 
     def __del__(self):
         try:

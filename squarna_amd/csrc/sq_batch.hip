@@ -59,6 +59,12 @@ static int64_t pow17_entries(const sq_paramset &ps, int maxn, double &scale)
     return entries <= (double)((int64_t)4 << 20) ? (int64_t)entries : 0;
 }
 
+// the job takes its bpp term from a matrix of probabilities in device memory (sq_batch_desc::bpp_matrix_dev)
+static inline bool dev_term(const sq_batch_desc *d, int j)
+{
+    return d->bpp_matrix_dev && d->bpp_matrix_dev[d->job_seq[j]] && d->psets[d->job_pset[j]].bpp != 0;
+}
+
 namespace {
 struct Layout {
     SqBatchSwitches sw;              // (sq_switches.h: read by plan)
@@ -116,7 +122,7 @@ JobNeed job_need(const sq_batch_desc *d, const Layout &L, int j)
     q.ld = ld_of(q.n, L.sw); q.nw = bits_nw(q.n); q.bpitch = bits_pitch(q.n);
     const bool ext = d->ext_score && d->ext_score[j];
     const bool own = d->mul_score && d->mul_score[j];
-    const bool term = d->bpp_term && d->bpp_term[j];
+    const bool term = (d->bpp_term && d->bpp_term[j]) || dev_term(d, j);      // (formed on the device: booked like an uploaded one)
     const bool shared = d->mul_shared && d->mul_shared[j];
     q.mulsh = (shared && !ext && L.mul_direct) ? 1 : 0;
     q.has_ext = ext ? 1 : (own || term || (shared && !q.mulsh)) ? 2 : 0;
@@ -389,6 +395,7 @@ struct BatchCreate {
     int upload_tail_tables();
     int upload_caller_matrices();
     int upload_shared_matrix();
+    int device_bpp_terms();
     int pinned_buffers();
 };
 
@@ -398,6 +405,22 @@ int BatchCreate::check_request(const void *ws, size_t ws_bytes) const
     if (((uintptr_t)ws & 255) != 0) { sq_set_error("workspace must be 256-byte aligned"); return -2; }
     for (int j = 0; j < d->njobs; j++) {
         const bool term = d->bpp_term && d->bpp_term[j];
+        const bool dterm = dev_term(d, j);
+        if (dterm) {
+            if (term || (d->mul_score && d->mul_score[j]) || (d->ext_score && d->ext_score[j]) || (d->mul_shared && d->mul_shared[j])) {
+                sq_set_error("a job of a sequence with bpp_matrix_dev takes its term from there: no bpp_term / mul_score / caller matrices / mul_shared");
+                return -4;
+            }
+            const double pw = std::fabs(d->psets[d->job_pset[j]].bpp);
+            if (pw != 0.5 && pw != 1.0) {
+                sq_set_error("bpp_matrix_dev: the device forms the term for |bpp| 0.5 and 1 only; other exponents take the host term "
+                             "(bpp_term), because the host libm's pow is the rule for them (DESIGN section 2)");
+                return -1;
+            }
+            const int n = d->seq_off[d->job_seq[j] + 1] - d->seq_off[d->job_seq[j]];
+            if (d->bpp_matrix_ld && d->bpp_matrix_ld[d->job_seq[j]] < n) { sq_set_error("bpp_matrix_ld below the sequence length"); return -1; }
+            continue;
+        }
         if (d->psets[d->job_pset[j]].bpp != 0 && !d->bpp_term) {
             sq_set_error("bpp != 0 paramsets need bpp_term: (bppm/max)^|bpp| from ViennaRNA's base-pair probabilities (SQRNdbnseq.py:341-364)");
             return -4;
@@ -667,9 +690,12 @@ void BatchCreate::job_records()
             mx = pset_maxabs[2 * J.pset + (def ? 0 : 1)];
             if (shared) mx *= std::fabs(d->mul_maxabs);
             else if (mul) {
-                const double *tm = term ? d->bpp_term[j] : d->mul_score[j];
-                double mm = 0;
-                for (size_t q = 0; q < nn; q++) mm = std::max(mm, std::fabs(tm[q]));
+                // a term formed on the device: (bppm / max) ** |bpp| has the maximum 1.0 exactly when max > 0, and the neutral
+                // term (max == 0: 1.0 multiplied, -0.0 added) stays below it -- maxabs is an UPPER BOUND of |cell| (the fp32
+                // prefilter margin of the scan, as mul_maxabs in the header says; no kernel takes a decision on its exact value)
+                const double *tm = dev_term(d, j) ? nullptr : term ? d->bpp_term[j] : d->mul_score[j];
+                double mm = tm ? 0 : 1.0;
+                for (size_t q = 0; tm && q < nn; q++) mm = std::max(mm, std::fabs(tm[q]));
                 mx = J.ext_add ? mx + mm : mx * mm;
             }
         }
@@ -783,7 +809,7 @@ int BatchCreate::open_uploads()
     own.enqueued = true;
     size_t want = (size_t)L.ltot * 16 + 8 * rftab.size() + 8 * powtab.size() + 8 * (size_t)L.pow_len + 4 * ((size_t)d->nseq + 1) + sizeof(SqJob) * d->njobs + sizeof(SqPsetDev) * d->npset + 8 * sdf.size() + 4 * rbpk.size() + 16384;
     for (int j = 0; j < d->njobs; j++)
-        if (b->jobs[j].has_ext && !(d->mul_shared && d->mul_shared[j])) want += (size_t)b->jobs[j].n * b->jobs[j].n * 8 * (b->jobs[j].has_ext == 1 ? 2 : 1);
+        if (b->jobs[j].has_ext && !(d->mul_shared && d->mul_shared[j]) && !dev_term(d, j)) want += (size_t)b->jobs[j].n * b->jobs[j].n * 8 * (b->jobs[j].has_ext == 1 ? 2 : 1);
     up.cap = std::min<size_t>(std::max<size_t>(want, (size_t)1 << 20), (size_t)64 << 20) & ~(size_t)255;
     void *pb = nullptr;
     if (sq_pinned_get(&pb, up.cap)) return 2;
@@ -844,7 +870,7 @@ int BatchCreate::upload_caller_matrices()
             if (!d->ext_bool || !d->ext_bool[j]) { sq_set_error("ext_score without ext_bool"); return -1; }
             up.put(b->ctx.mat64 + J.mat64_off, d->ext_score[j], nn);
             up.put(b->ctx.mat64 + J.mat64_off + (int64_t)J.n * J.n, d->ext_bool[j], nn);
-        } else if (J.has_ext == 2 && !(d->mul_shared && d->mul_shared[j])) {
+        } else if (J.has_ext == 2 && !(d->mul_shared && d->mul_shared[j]) && !dev_term(d, j)) {
             up.put(b->ctx.mat64 + J.mat64_off, (d->bpp_term && d->bpp_term[j]) ? d->bpp_term[j] : d->mul_score[j], nn);
         }
     }
@@ -872,6 +898,62 @@ int BatchCreate::upload_shared_matrix()
         sq_launch_gather_mul(b->ctx, d_jl, (int)jl.size(), L.maxn, st);
         if (sq_check(hipGetLastError(), "sq_gather_mul_kernel")) return 2;
     }
+    return up.rc;
+}
+
+// ---- bpp terms from probabilities in device memory (sq_bpp_dev.hip) ----
+int BatchCreate::device_bpp_terms()
+{
+    if (!d->bpp_matrix_dev) return 0;
+    // per sequence with a matrix and bpp != 0 jobs: one record and the list of those jobs
+    std::vector<int32_t> cnt((size_t)d->nseq + 1, 0);
+    for (int j = 0; j < d->njobs; j++) if (dev_term(d, j)) cnt[(size_t)d->job_seq[j] + 1]++;
+    for (int s = 0; s < d->nseq; s++) cnt[(size_t)s + 1] += cnt[s];
+    std::vector<SqBppJob> jl((size_t)cnt[d->nseq]);
+    std::vector<int32_t> fill(cnt.begin(), cnt.end() - 1);
+    std::vector<SqBppSeq> recs;
+    int64_t max_units = 1;
+    for (int j = 0; j < d->njobs; j++) {
+        if (!dev_term(d, j)) continue;
+        const SqJob &J = b->jobs[j];
+        const double pw = d->psets[J.pset].bpp;
+        jl[(size_t)fill[J.seq]++] = SqBppJob{J.mat64_off, j, (std::fabs(pw) == 0.5 ? 1 : 0) | (pw < 0 ? 2 : 0)};
+    }
+    for (int s = 0; s < d->nseq; s++) {
+        if (cnt[(size_t)s + 1] == cnt[s]) continue;
+        SqBppSeq q{};
+        q.src = d->bpp_matrix_dev[s]; q.n = d->seq_off[s + 1] - d->seq_off[s];
+        q.ld = d->bpp_matrix_ld ? d->bpp_matrix_ld[s] : q.n;
+        q.job0 = cnt[s]; q.njob = cnt[(size_t)s + 1] - cnt[s];
+        for (int t = 0; t < q.njob; t++) q.any_sqrt |= jl[(size_t)q.job0 + t].mode & 1;
+        if (q.n <= 0) continue;
+        max_units = std::max(max_units, sq_bpp_units(q.n, q.ld));
+        recs.push_back(q);
+    }
+    if (recs.empty()) return 0;
+    // (the maxima and the two lists travel in the candidate arena's first bytes: nothing else uses it before the first fold,
+    // and the stream orders them behind the shared matrix's job list)
+    const size_t o_seq = align_up(8 * recs.size(), 256), o_job = align_up(o_seq + sizeof(SqBppSeq) * recs.size(), 256);
+    if (o_job + sizeof(SqBppJob) * jl.size() > sizeof(SqCand) * (size_t)L.cand_records) { sq_set_error("bpp_matrix_dev: the job lists outgrow the candidate arena"); return -1; }
+    char *arena = base + L.off_cands;
+    unsigned long long *d_max = reinterpret_cast<unsigned long long *>(arena);
+    if (sq_check(hipMemsetAsync(d_max, 0, 8 * recs.size(), b->stream), "bpp maxima")) return 2;
+    up.put(arena + o_seq, recs.data(), sizeof(SqBppSeq) * recs.size());
+    if (up.put(arena + o_job, jl.data(), sizeof(SqBppJob) * jl.size())) return up.rc;         // (no kernel over lists that did not arrive)
+    // (slot 9 of sq_profile_get: the two kernels between a pair of events, always -- profiling cannot be enabled before the
+    // batch exists; the events go back to the slot's pool with the first sq_profile_get and are destroyed with the batch)
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { if (e0) hipEventDestroy(e0); e0 = e1 = nullptr; }
+    if (e0) hipEventRecord(e0, b->stream);
+    sq_launch_bpp_terms(b->ctx, reinterpret_cast<const SqBppSeq *>(arena + o_seq), (int)recs.size(),
+                        reinterpret_cast<const SqBppJob *>(arena + o_job), d_max, max_units, b->stream);
+    if (e0) {
+        hipEventRecord(e1, b->stream);
+        ProfSlot &ps = b->prof[9];
+        ps.pending.emplace_back(e0, e1); ps.launches += 2;
+        for (const SqBppSeq &q : recs) ps.bytes += 8.0 * q.n * q.n * (2 + q.njob);       // read for the maximum, read again, one write per job
+    }
+    if (sq_check(hipGetLastError(), "sq_bpp_term_kernel")) return 2;
     return up.rc;
 }
 
@@ -943,7 +1025,7 @@ extern "C" int sq_batch_create(sq_batch **out, const sq_batch_desc *d, void *ws,
     c.carve();
     if ((rc = c.open_uploads())) return rc;
     c.prof.mark("carve");
-    if ((rc = c.upload_inputs()) || (rc = c.upload_tail_tables()) || (rc = c.upload_caller_matrices()) || (rc = c.upload_shared_matrix())) return rc;
+    if ((rc = c.upload_inputs()) || (rc = c.upload_tail_tables()) || (rc = c.upload_caller_matrices()) || (rc = c.upload_shared_matrix()) || (rc = c.device_bpp_terms())) return rc;
     c.prof.mark("uploads");
     if ((rc = c.pinned_buffers())) return rc;
     set_lanes(c.b);

@@ -299,3 +299,27 @@ __host__ __device__ static inline size_t sq_extend_lds_bytes(int T) { const size
 void sq_launch_gather_mul(const SqDevCtx &c, const int32_t *job_list, int njl, int maxn, hipStream_t st, double *dst_one = nullptr);
 // the caller's row-major L x L matrix -> the diagonal-major copy the kernels read (SqDevCtx::mulM)
 void sq_launch_mul_diag(const double *M, int L, double *dst, hipStream_t st);
+
+// sq_bpp_dev.hip: the bpp terms of the jobs of sequences whose base-pair probabilities live on the device
+// (sq_batch_desc::bpp_matrix_dev; SQRNdbnseq.py:341-364)
+#define SQ_BPP_CHUNK 2048            // doubles per chunk of a row: 256 threads x 4 pairs (even: chunk starts keep the row's parity)
+struct SqBppSeq {
+    const double *src;               // the caller's N x N matrix, rows ld doubles apart (ld == n: dense, walked as one row of n^2)
+    int32_t ld, n;
+    int32_t job0, njob;              // its bpp != 0 jobs: SqBppJob records [job0, job0 + njob)
+    int32_t any_sqrt, reserved;      // some job has |bpp| == 0.5
+};
+struct SqBppJob {
+    int64_t dst_off;                 // SqJob::mat64_off
+    int32_t job;                     // index into SqDevCtx::jobs
+    int32_t mode;                    // bit 0: sqrt(q) (|bpp| == 0.5; else q), bit 1: the term is added (bpp < 0)
+};
+// chunks one sequence's matrix is walked in (the kernels' SqBppWalk)
+static inline int64_t sq_bpp_units(int32_t n, int32_t ld)
+{
+    const int64_t len = ld == n ? (int64_t)n * n : n;
+    return (ld == n ? 1 : (int64_t)n) * ((len + SQ_BPP_CHUNK - 1) / SQ_BPP_CHUNK);
+}
+// d_maxbits: nrec zeroed 64-bit words (the maxima's bit patterns); max_units: the largest sq_bpp_units of the sequences
+void sq_launch_bpp_terms(const SqDevCtx &c, const SqBppSeq *d_seqs, int nrec, const SqBppJob *d_jobs, unsigned long long *d_maxbits,
+                         int64_t max_units, hipStream_t st);

@@ -217,7 +217,8 @@ struct sq_batch {
     int64_t mwm_stats[6] = {0, 0, 0, 0, 0, 0};   // blossom jobs collected, their scan passes; the job with the most passes:
                                                  // its passes, events, vertices, edges (reset by sq_profile_reset)
     bool prof_on = false;
-    ProfSlot prof[9];                     // 0 fill, 1 state, 2 scan, 3 score, 4 Edmonds, 5 Hungarian, 6 Nussinov, 7 persistent rounds (sq_rounds.hip), 8 the alignment's scatter
+    ProfSlot prof[10];                    // 0 fill, 1 state, 2 scan, 3 score, 4 Edmonds, 5 Hungarian, 6 Nussinov, 7 persistent rounds (sq_rounds.hip), 8 the alignment's scatter,
+                                          // 9 the bpp terms formed at sq_batch_create (sq_bpp_dev.hip; recorded whether profiling is on or not: it cannot be on yet)
 };
 
 // CPU accounting (SQ_CPUACC=1): thread CPU time spent in the host phases, summed over all threads, printed per fold.

@@ -19,7 +19,7 @@ from .dbn import gap_mask
 from .records import Prepared, PackedRows  # noqa: F401
 from .batch import Batch, fold_concurrently
 from .results import unpack_result, packed_pair_tables, _Blocks, _BlockRun  # noqa: F401
-from .bpp import vienna_bpp, set_bpp_provider, bpp_terms  # noqa: F401
+from .bpp import vienna_bpp, set_bpp_provider, bpp_terms, check_bpp_matrix  # noqa: F401
 from .plan import (pool_slots_wanted, pool_slots_wanted_many, pool_slot_cap, slot_bytes, default_structs,  # noqa: F401
                    MIN_CAND_PER_NT, SubBatchPlan, _kept_bytes_per_slot, _free_device_bytes, _shared_weights)
 
@@ -31,7 +31,8 @@ def _cut_in_two_lanes(groups, hints, tensors=False):
     if len(groups) == 1 and switches.engine_lanes() >= 2 and len(groups[0]) >= 256 and hints[0] is None and not tensors:
         recs = groups[0]
         cost = [float(len(r[0])) ** 2 * len(r[4]) for r in recs]
-        if sum(cost) >= 1e8 and not any(len(r) > 5 and r[5] is not None and hasattr(r[5], "is_cuda") for r in recs):
+        if sum(cost) >= 1e8 and not any(len(r) > 5 and r[5] is not None and hasattr(r[5], "is_cuda") for r in recs) \
+                and not any(_bpp_of(r) is not None for r in recs):
             from .parallel import lpt_partition
             back = [p for p in lpt_partition(cost, 2) if p]
             return [[recs[k] for k in idx] for idx in back], [None] * len(back), back
@@ -81,6 +82,27 @@ def _block_results(batches, groups, cfg):
 
 
 _TABLES = ("partner", "scores", "pset_mask", "metrics", "row_off", "cell_off")
+
+#: where a record carries its device matrix of base-pair probabilities (0..5: the fold's fields, 6..8: Predict's block fields)
+_BPP_AT = 9
+
+
+def _with_bpp(records, bpp):
+    """The records with their matrices of base-pair probabilities behind them (index _BPP_AT), so that whatever slices,
+    reorders or repeats the records -- sub-batches, lanes, the capacity retry -- carries each matrix with its record.
+    bpp: per record a CUDA float64 tensor of the record's gap-free length (separators counted) squared, or None."""
+    if len(bpp) != len(records):
+        raise ValueError("bpp: %d matrices for %d records" % (len(bpp), len(records)))
+    out = []
+    for k, (r, m) in enumerate(zip(records, bpp)):
+        if m is not None:
+            check_bpp_matrix(m, int(np.count_nonzero(~gap_mask(r[0]))), "bpp matrix of record %d" % k)
+        out.append(tuple(r[:_BPP_AT]) + (None,) * (_BPP_AT - len(r)) + (m,))
+    return out
+
+
+def _bpp_of(r):
+    return r[_BPP_AT] if len(r) > _BPP_AT else None
 
 
 class _TensorRun:
@@ -175,9 +197,16 @@ class HipEngine:
         # L x L device matrix (200 MB at L = 5000) alive after the alignment that owns it has ended
         self._sm_maxabs = (None, None)
 
-    def fold_records(self, records, **opts):
+    def fold_records(self, records, bpp=None, **opts):
         """records: list of (seq, reacts, restraints, dbn, paramsets, stemmatrix);
-        returns the list of SQRNdbnseq return tuples, in order."""
+        returns the list of SQRNdbnseq return tuples, in order.
+        bpp: per record a CUDA float64 N x N tensor of base-pair probabilities (N = the gap-free length, separators counted:
+        what the reference hands to ViennaRNA), or None -- it takes the provider's place for that record, and the terms of its
+        bpp != 0 paramsets are formed on the device (|bpp| 0.5 or 1; a record with another exponent has its matrix copied
+        to the host once and takes the host terms of bpp.bpp_terms).  ValueError on a wrong size, dtype, device or a strided
+        column.  The tensors are read, never written; a repeated fold (capacity retry) reads them again."""
+        if bpp is not None:
+            records = _with_bpp(records, bpp)
         # Building tens of thousands of small containers (Prepared records, result tuples) with the cyclic collector on
         # costs ~10 us per record in generation scans of objects that hold no cycles: 220 of 340 ms for 10,000 records.
         import gc
@@ -189,23 +218,23 @@ class HipEngine:
             if was:
                 gc.enable()
 
-    def fold_records_packed(self, records, **opts):
+    def fold_records_packed(self, records, bpp=None, **opts):
         """Like fold_records, but every record's result stays in the library's packed form (bytes, sq_result_pack layout):
         the payload ranks exchange (parallel.py).  `unpack_result(Prepared(...), blob)` decodes one on any rank."""
-        return self.fold_records(records, _packed=True, **opts)
+        return self.fold_records(records, bpp=bpp, _packed=True, **opts)
 
-    def fold_tensors(self, records, **opts):
+    def fold_tensors(self, records, bpp=None, **opts):
         """Like fold_records, but the results stay on the device as data: dict of torch tensors partner int32[cells],
         scores float64[rows, 3], pset_mask int64[rows], metrics float64[records, 16], row_off / cell_off int64[records + 1]
         in the layout of sq_result_pairs_dev (include/squarna_hip.h; gap-free coordinates), the host arrays nstruct and
         lengths (int64 per record), and source: "device" when the ranking tail of every batch ran on the device, "host"
         when none did (rankbydiff, forced hardrest pairs, conslim > 1, > 4,096 final structures: converted from the packed
-        records), "mixed" otherwise.  `keep` as for fold_records."""
+        records), "mixed" otherwise.  `keep` and `bpp` as for fold_records."""
         import torch
         if not records:
             raise ValueError("fold_tensors needs at least one record")
         kept = self.last_ref_scores                                  # (the known structures' scores are in the metrics table)
-        out = self.fold_records(records, _tensors=True, **opts)
+        out = self.fold_records(records, bpp=bpp, _tensors=True, **opts)
         self.last_ref_scores = kept
         # every record carries (the tables of its batch, its place in them): the batches must cover the records in order,
         # each whole -- what the sub-batch planner hands out; anything else would join the tables in another order
@@ -253,7 +282,8 @@ class HipEngine:
         # for the 500-vertex Edmonds graphs of its records however few they are.  Off by default.
         # Not the rows weighted by ONE device matrix: they share that tensor on the caller's stream.
         lanes = switches.engine_sublanes()
-        if direct or sum(dense) > 0 or opts.get("_blocks") or opts.get("_tensors"):
+        # Nor records with their probabilities on the device: those tensors are complete on the caller's stream.
+        if direct or sum(dense) > 0 or opts.get("_blocks") or opts.get("_tensors") or any(_bpp_of(r) is not None for r in records):
             lanes = 1
         mkey = (tuple(tuple(sorted((k, str(v)) for k, v in ps.items())) for ps in records[0][4]),       # (the paramsets by content: an id() is reused)
                 int(opts.get("poollim", 1000)), max(len(r[0]) for r in records) // 64)
@@ -305,7 +335,9 @@ class HipEngine:
         M, B = opts.pop("M", 1.8), opts.pop("B", -0.6)
         prepared = [Prepared(r[0], r[1], r[2], r[3]) for r in records]
         psets = [r[4] for r in records]
-        bpp = bpp_terms(prepared, psets, M, B)
+        # (a record's matrix of probabilities on the device -- given with the record, or returned by the provider -- is handed
+        # to the batch as it is: the same unmodified tensor for every batch built from the record)
+        bpp, bpp_dev = bpp_terms(prepared, psets, M, B, given=[_bpp_of(r) for r in records], device=True)
         mul = None
         mul_shared = None
         if _shared_weights(records):
@@ -340,7 +372,7 @@ class HipEngine:
             cand = int(max(cand, MIN_CAND_PER_NT, 0.117 * 1.6 * nmax * runs) * grow[0]) + 1
         b = Batch(prepared, psets, interchainonly=interchainonly, mul=mul, fp32=False, bpp=bpp,
                   max_structs=max_structs * grow[1], cand_per_nt=cand, mul_shared=mul_shared,
-                  pool_lists=opts.get("poollim", 1000) > 1 and mul_shared is None)
+                  pool_lists=opts.get("poollim", 1000) > 1 and mul_shared is None, bpp_dev=bpp_dev)
         b.limit_results(keep)
         return b, opts
 

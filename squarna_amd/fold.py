@@ -232,7 +232,7 @@ def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, i
          alignment=False, evalonly=False, entropy=False, rfam=False, g4=False, rbp=False,
          i=None, ff=None, c=None, config=None, s=None, seq=None, algo=None, algorithm=None, rb=None, ll=None, levlim=None,
          tl=None, ol=None, cl=None, pl=None, pr=None, msn=None, hr=None, ico=None, iw=None, ignore=None, a=None, ali=None,
-         eo=None, inputrestr=None):
+         eo=None, inputrestr=None, bpp=None):
     """Predict the structures of every input record and return them as a :class:`FoldResult`.
 
     The inputs (``inputfile`` / ``inputseq``), the prediction keywords, their defaults, synonyms, validation messages and the
@@ -240,7 +240,16 @@ def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, i
     instead: sequences, or (name, sequence, reactivities, restraints, reference) tuples with None for what a record lacks.
     ``outplim`` (default: ``toplim``) bounds the structures kept per record.  Alignment mode has a function of its own:
     use ``FoldAlignment``.  ``evalonly``, ``entropy`` and the ``rfam`` / ``g4`` / ``rbp`` restraint searches belong to
-    ``Predict``.  All of these raise ValueError here."""
+    ``Predict``.  All of these raise ValueError here.
+
+    ``bpp`` gives the base-pair probabilities of the records for the ``bpp != 0`` paramsets (7 of the default
+    configuration's 12) instead of the host provider (ViennaRNA): a list with one square matrix or None per record, or one
+    ``[R, Lmax, Lmax]`` tensor whose leading N x N corner is record r's matrix -- N is the record's gap-free length with
+    separators counted, what the reference hands to ViennaRNA.  CUDA float64 tensors are used where they are (a corner of
+    the 3-D form is passed as a strided view, not copied) and the terms are formed on the GPU; float32 tensors are widened on
+    their device; CPU tensors and arrays are uploaded once per record, not once per paramset.  The tensors are not modified.
+    With an engine without ``fold_tensors`` the matrices go through the provider hook (``set_bpp_provider``) instead; records
+    with the same sequence must then carry the same matrix."""
     def pick(cur, *alts):
         for alt in alts:
             if alt is not None:
@@ -331,6 +340,7 @@ def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, i
     seqs = [rec[1] for rec in inputs]
     psnames = [config_for(sq)[0] for sq in seqs]
     parts = []
+    mats = _bpp_matrices(bpp, seqs, hasattr(eng, "fold_tensors")) if bpp is not None else None
 
     def flush(batch):
         # records with different priority index sets cannot share one fold call (as in Predict)
@@ -340,10 +350,12 @@ def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, i
         for prio, idx in groups.items():
             recs = [(inputs[k][1], inputs[k][2], inputs[k][3], inputs[k][4], config_for(seqs[k])[1], None) for k in idx]
             if hasattr(eng, "fold_tensors"):
-                t = eng.fold_tensors(recs, priority=set(prio), **common)
+                given = dict(bpp=[mats[k] for k in idx]) if mats is not None else {}
+                t = eng.fold_tensors(recs, priority=set(prio), **given, **common)
                 parts.append((t, t["nstruct"], t["lengths"], idx, True, t["source"]))
             else:
-                res = eng.fold_records(recs, priority=set(prio), **common)
+                with _given_to_provider(mats, seqs, idx):
+                    res = eng.fold_records(recs, priority=set(prio), **common)
                 refsc = getattr(eng, "last_ref_scores", None) or [None] * len(idx)
                 full = [(r, seqs[k], (rs if rs is not None else _ref_scores(inputs[k])) if inputs[k][4] else None)
                         for r, k, rs in zip(res, idx, refsc)]
@@ -362,6 +374,72 @@ def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, i
     tables, nstruct, lengths = _join([p[:5] for p in parts], seqs)
     return FoldResult([rec[0] for rec in inputs], seqs, psnames, tables, nstruct, lengths,
                       sources.pop() if len(sources) == 1 else "mixed")
+
+
+def _bpp_matrices(bpp, seqs, on_device):
+    """Fold's bpp argument as one matrix or None per record: float64 N x N, N the record's gap-free length (separators
+    counted).  on_device: CUDA torch tensors for HipEngine.fold_tensors (tensors already there are views, not copies; fp32
+    is widened on its device; host data is uploaded once per record).  Else numpy arrays for the provider hook."""
+    import torch
+    R = len(seqs)
+    lens = [int(np.count_nonzero(~gap_mask(sq))) for sq in seqs]
+    if hasattr(bpp, "dim") and bpp.dim() == 3 or isinstance(bpp, np.ndarray) and bpp.ndim == 3:
+        if bpp.shape[0] != R or bpp.shape[1] != bpp.shape[2] or bpp.shape[1] < max(lens):
+            raise ValueError("bpp: shape %s; [%d, Lmax, Lmax] with Lmax >= %d is needed" % (tuple(bpp.shape), R, max(lens)))
+        bpp = [bpp[k, :n, :n] for k, n in enumerate(lens)]
+    elif len(bpp) != R:
+        raise ValueError("bpp: %d matrices for %d records" % (len(bpp), R))
+    out = []
+    for k, (m, n) in enumerate(zip(bpp, lens)):
+        if m is None:
+            out.append(None)
+            continue
+        if not hasattr(m, "is_cuda"):
+            m = torch.from_numpy(np.ascontiguousarray(m, dtype=np.float64))
+        if m.dim() != 2 or tuple(m.shape) != (n, n):
+            raise ValueError("bpp[%d]: shape %s, the record needs %d x %d (its gap-free length, separators counted)" % (k, tuple(m.shape), n, n))
+        if m.dtype not in (torch.float64, torch.float32):
+            raise ValueError("bpp[%d]: dtype %s; float64 or float32 is needed" % (k, m.dtype))
+        if not on_device:
+            out.append(m.detach().double().cpu().numpy())
+            continue
+        if m.dtype != torch.float64:
+            m = m.double()
+        if not m.is_cuda:
+            m = m.to(torch.device("cuda", torch.cuda.current_device()))
+        if n > 1 and m.stride(1) != 1:
+            m = m.contiguous()
+        out.append(m)
+    return out
+
+
+@contextlib.contextmanager
+def _given_to_provider(mats, seqs, idx):
+    """For an engine without fold_tensors: the given matrices of records idx answer the provider hook, by gap-free
+    sequence; every other sequence falls through to the provider installed before."""
+    if mats is None or all(mats[k] is None for k in idx):
+        yield
+        return
+    from .records import Prepared
+    table = {}
+    for k in idx:
+        if mats[k] is None:
+            continue
+        key = Prepared(seqs[k]).shortseq
+        if key in table and not np.array_equal(table[key], mats[k]):
+            raise ValueError("bpp: two records with the sequence of record %d carry different matrices" % k)
+        table[key] = mats[k]
+
+    def provider(shortseq, reacts, M, B):
+        m = table.get(shortseq)
+        if m is None:
+            return old(shortseq, reacts, M, B)
+        return m if np.max(m, initial=0.0) > 0 else None                # (:350,360)
+    old = _engine.set_bpp_provider(provider)
+    try:
+        yield
+    finally:
+        _engine.set_bpp_provider(old)
 
 
 def _ref_scores(rec):

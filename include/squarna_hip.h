@@ -481,6 +481,59 @@ SQ_API int sq_profile_reset(sq_batch *b);
  * vertices, out[5] its edges. */
 SQ_API int sq_profile_counters(sq_batch *b, int32_t kernel, int64_t out[6]);
 
+/* ---- scores and metrics of GIVEN structures (SQRNdbnseq.py:958-970, 861-899, 498-517, 1249-1258) -----------------------
+ * sq_score_structs_dev -- for every partner row: ReferenceScores of the structure under its record (ScoreStruct of
+ * PairsToStems(sorted pairs) in gap-free coordinates, with the host libm's powers), its stems, and TP FP FN FS PR RC against the
+ * record's known structure; for every record the three scores of its known structure.  No sq_batch.  All pointers are the
+ * caller's DEVICE memory; everything is enqueued on hip_stream, nothing is allocated or waited for.
+ * Records (sq_score_desc), arrays over the gap-free positions of all records, record r from d_pos_off[r] on: d_codes (letter
+ * codes as for sq_batch_desc, after upper() and T -> U), d_reacts (NULL when max_react_len is 0), d_gfcol (the input column of
+ * every position), d_known (the known structure's partner in gap-free coordinates, -1 unpaired).  Per record: d_has_reacts
+ * (0: every reactivity is 0.5, d_reacts is not read), d_nsep (its separators), d_known_n (pairs of the known structure, -1: none).
+ * d_colmap, record r from d_col_off[r] on: the gap-free position of every input column, -1 for a gap column.  d_col_off /
+ * d_colmap / d_gfcol are NULL when no record has a gap column.  d_pow[k] = pow(k / 2, 1.7) of the host's libm, k < pow_len
+ * (4 x the longest record + 1 covers every stem).  max_react_len: the longest gap-free length of a record with reactivities
+ * (<= 32768; sizes the kernel's LDS bitmap).
+ * Rows (sq_score_rows): row q is record d_row_rec[q]'s and starts at d_partner[d_row_start[q]]: one int32 per INPUT column
+ * of the record, the partner's column or -1.  Outputs per row: d_status (0; 1 invalid: a partner outside the record, p[p[i]]
+ * != i, p[i] == i, a pair on a separator, or a record without a position to score; 2: beyond the exact range of the
+ * rounding -- the caller recomputes that row), d_npairs and d_nstems (after the pairs that touch a gap column are dropped),
+ * d_scores [nrows][3], d_metrics [nrows][6] (NaN without a known structure; both NaN for an invalid row), d_stems [stem_cap][3]
+ * = (i, j, len) in input columns, row q's from d_stem_off[q] on.  Per record: d_ref_scores [nrec][3] (NaN without a known
+ * structure), d_ref_status [nrec].
+ * pass 0 writes d_status, d_npairs, d_nstems (and d_ref_status); the caller forms d_stem_off int64[nrows + 1], the exclusive
+ * scan of d_nstems, and sizes d_stems; pass 1 writes the rest.  d_scratch: sq_score_scratch(nrec) bytes, the same for both
+ * passes.  Returns 0, or -1 (bad argument, scratch too small: nothing enqueued). */
+typedef struct sq_score_desc {
+    int32_t nrec, max_react_len;
+    const int64_t *d_pos_off;       /* [nrec + 1] */
+    const uint8_t *d_codes;
+    const double *d_reacts;
+    const uint8_t *d_has_reacts;    /* [nrec] */
+    const int32_t *d_nsep;          /* [nrec] */
+    const int64_t *d_col_off;       /* [nrec + 1] or NULL */
+    const int32_t *d_colmap, *d_gfcol;
+    const int32_t *d_known, *d_known_n;
+    const double *d_pow;
+    int32_t pow_len;
+} sq_score_desc;
+typedef struct sq_score_rows {
+    int64_t nrows;
+    const int32_t *d_partner;
+    const int64_t *d_row_start;     /* [nrows] */
+    const int32_t *d_row_rec;       /* [nrows] */
+    int32_t *d_status, *d_npairs, *d_nstems;
+    const int64_t *d_stem_off;      /* [nrows + 1], pass 1 */
+    int32_t *d_stems;
+    int64_t stem_cap;
+    double *d_scores, *d_metrics;
+    double *d_ref_scores;
+    int32_t *d_ref_status;
+} sq_score_rows;
+SQ_API size_t sq_score_scratch(int32_t nrec);
+SQ_API int sq_score_structs_dev(const sq_score_desc *d, const sq_score_rows *o, int32_t pass, void *d_scratch, size_t scratch_bytes,
+                                void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

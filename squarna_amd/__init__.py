@@ -17,6 +17,7 @@ from .config import ParseConfig  # noqa: F401,E402
 from .api import Predict, Main  # noqa: F401,E402
 from .fold import Fold, FoldResult  # noqa: F401,E402
 from .fold_align import FoldAlignment, AlignmentResult  # noqa: F401,E402
+from .score import Score, ScoreResult  # noqa: F401,E402
 from .core import (BPMatrix, AnnotateStems, OptimalStems, RunAlgo, Edmonds, Hungarian, Nussinov,  # noqa: F401,E402
                    SQRNdbnseq, RunSQRNdbnseq, ScoreStruct, ReferenceScores)
 
@@ -27,5 +28,5 @@ def BuildRfam(*args, **kwargs):
     raise NotImplementedError("BuildRfam is out of scope of squarna_amd (see DESIGN.md)")
 
 
-__all__ = ["Predict", "Main", "Fold", "FoldResult", "FoldAlignment", "AlignmentResult", "BuildRfam", "ParseConfig", "BPMatrix", "AnnotateStems", "OptimalStems", "RunAlgo",
+__all__ = ["Predict", "Main", "Fold", "FoldResult", "FoldAlignment", "AlignmentResult", "Score", "ScoreResult", "BuildRfam", "ParseConfig", "BPMatrix", "AnnotateStems", "OptimalStems", "RunAlgo",
            "Edmonds", "Hungarian", "Nussinov", "SQRNdbnseq", "RunSQRNdbnseq"]

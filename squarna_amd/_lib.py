@@ -24,7 +24,8 @@ SYMBOLS = ["sq_version", "sq_last_error", "sq_last_capacity", "sq_batch_workspac
            "sq_mwm_workspace_bytes", "sq_mwm", "sq_lsap_workspace_bytes", "sq_lsap",
            "sq_nussinov_workspace_bytes", "sq_nussinov", "sq_dbn_pairs", "sq_write_blocks", "sq_parse_default",
            "sq_host_cache_trim", "sq_align_first_fit", "sq_result_pairs_size", "sq_result_pairs_dev",
-           "sq_align_pair_count_scratch", "sq_align_pair_count", "sq_first_fit_scratch", "sq_first_fit_dev"]
+           "sq_align_pair_count_scratch", "sq_align_pair_count", "sq_first_fit_scratch", "sq_first_fit_dev",
+           "sq_score_scratch", "sq_score_structs_dev"]
 
 BATCH_NO_FP32 = 1
 BATCH_POOL_LISTS = 2
@@ -80,6 +81,22 @@ class BlockDesc(C.Structure):
     _fields_ = [("nrec", C.c_int32), ("names", C.c_char_p), ("seqs", C.c_char_p), ("reacts", C.c_char_p),
                 ("restr", C.c_char_p), ("refs", C.c_char_p), ("nameset", C.POINTER(C.c_int32)),
                 ("psnames", C.POINTER(C.c_char_p)), ("nsets", C.c_int32), ("conslim", C.c_int32), ("outplim", C.c_int32)]
+
+
+class ScoreDesc(C.Structure):
+    """sq_score_desc: the records of sq_score_structs_dev (device pointers)."""
+    _fields_ = [("nrec", C.c_int32), ("max_react_len", C.c_int32), ("d_pos_off", C.c_void_p), ("d_codes", C.c_void_p),
+                ("d_reacts", C.c_void_p), ("d_has_reacts", C.c_void_p), ("d_nsep", C.c_void_p), ("d_col_off", C.c_void_p),
+                ("d_colmap", C.c_void_p), ("d_gfcol", C.c_void_p), ("d_known", C.c_void_p), ("d_known_n", C.c_void_p),
+                ("d_pow", C.c_void_p), ("pow_len", C.c_int32)]
+
+
+class ScoreRows(C.Structure):
+    """sq_score_rows: the partner rows of sq_score_structs_dev and where their results go (device pointers)."""
+    _fields_ = [("nrows", C.c_int64), ("d_partner", C.c_void_p), ("d_row_start", C.c_void_p), ("d_row_rec", C.c_void_p),
+                ("d_status", C.c_void_p), ("d_npairs", C.c_void_p), ("d_nstems", C.c_void_p), ("d_stem_off", C.c_void_p),
+                ("d_stems", C.c_void_p), ("stem_cap", C.c_int64), ("d_scores", C.c_void_p), ("d_metrics", C.c_void_p),
+                ("d_ref_scores", C.c_void_p), ("d_ref_status", C.c_void_p)]
 
 
 class FoldOpts(C.Structure):
@@ -171,6 +188,9 @@ def load():
     L.sq_first_fit_scratch.argtypes = [C.c_int64, C.c_int32]
     L.sq_first_fit_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                    C.c_void_p]
+    L.sq_score_scratch.restype = C.c_size_t
+    L.sq_score_scratch.argtypes = [C.c_int32]
+    L.sq_score_structs_dev.argtypes = [C.POINTER(ScoreDesc), C.POINTER(ScoreRows), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
     L.sq_mwm_workspace_bytes.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
     L.sq_mwm.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                          C.c_void_p, C.c_size_t, C.c_void_p]

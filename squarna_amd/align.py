@@ -82,7 +82,13 @@ def Metrics(ref, pred):
     """SQRNdbnali.py:195-208."""
     if not ref:
         return [np.nan] * 6
-    rb, pb = set(DBNToPairs(ref)), set(DBNToPairs(pred))
+    return PairMetrics(DBNToPairs(ref), DBNToPairs(pred))
+
+
+def PairMetrics(refpairs, predpairs):
+    """Metrics' numbers (SQRNdbnali.py:200-208, SQRNdbnseq.py:1250-1258) from the two sets of pairs themselves: for callers
+    that hold pairs, whose bracket text may not be writable (levels beyond the alphabet print as dots)."""
+    rb, pb = set(refpairs), set(predpairs)
     TP, FP, FN = len(pb & rb), len(pb - rb), len(rb - pb)
     PRC = (round(TP / (TP + FP), 3)) if (TP + FP) else 1
     RCL = (round(TP / (TP + FN), 3)) if (TP + FN) else 1

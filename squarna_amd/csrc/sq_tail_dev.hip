@@ -21,36 +21,7 @@
 #include "../../include/squarna_hip.h"
 #include "sq_tail_dev.h"
 #include "sq_extend.h"
-
-// ---- Python's round(x, 3) (SQRNdbnseq.py:891-893,1256-1258): the decimal nearest to the EXACT binary value, ties to
-// even, then the double nearest to that decimal.  x = m 2^e exactly, so 1000 x = (1000 m) / 2^-e is an integer
-// quotient and remainder in 64-bit arithmetic; k / 1000.0 is one correctly rounded division of exact integers, i.e. what
-// strtod returns for the decimal's text.  Exact for |x| < 2^53 / 1000; beyond, *inexact is set (the host tail takes over).
-__device__ __forceinline__ double sq_round3(double x, uint32_t *inexact)
-{
-    if (!(x == x) || fabs(x) == INFINITY) return x;
-    const double ax = fabs(x);
-    if (ax >= 4503599627370496.0) return x;                            // >= 2^52: an integer
-    if (ax >= 9.0e12) { *inexact = 1; return x; }
-    const unsigned long long bits = (unsigned long long)__double_as_longlong(ax);
-    const int ex = (int)((bits >> 52) & 0x7FFull);
-    unsigned long long m = bits & 0xFFFFFFFFFFFFFull;
-    int e;
-    if (ex == 0) e = -1074; else { m |= 1ull << 52; e = ex - 1075; }
-    unsigned long long k;
-    if (e >= 0) k = (m << e) * 1000ull;                                // (ax < 9e12: no overflow)
-    else {
-        const int E = -e;
-        const unsigned long long p = m * 1000ull;                      // < 2^63
-        if (E >= 64) k = 0ull;                                         // 1000 x < 1/2
-        else {
-            const unsigned long long q = p >> E, r = p & ((1ull << E) - 1ull), half = 1ull << (E - 1);
-            k = q + ((r > half || (r == half && (q & 1ull))) ? 1ull : 0ull);
-        }
-    }
-    const double res = (double)k / 1000.0;
-    return x < 0 ? -res : res;
-}
+#include "sq_scoring.h"                // sq_round3, sq_pair_value, sq_prf_counts
 
 __device__ __forceinline__ unsigned long long sq_mix_stem(int i, int j, int len)
 {
@@ -145,13 +116,7 @@ __device__ __forceinline__ void sq_score_struct_wave(const SqDevCtx &c, const Sq
             double bpsum = 0;
             for (int k = 0; k < s.len; k++) {
                 const int v = s.i + k, w = s.j - k;
-                const int a = codes[v], b = codes[w];
-                const int A = 0, C = 2, G = 6, U = 20;
-                double bp = 0.0;
-                if ((a == G && b == U) || (a == U && b == G)) bp = -0.5;
-                else if ((a == A && b == U) || (a == U && b == A)) bp = 1.5;
-                else if ((a == G && b == C) || (a == C && b == G)) bp = 4.0;
-                bpsum += bp;                                           // (multiples of 1/2: exact in any order)
+                bpsum += sq_pair_value(codes[v], codes[w]);            // (multiples of 1/2: exact in any order)
                 if (marks) { atomicOr(&s_bits[v >> 5], 1u << (v & 31)); atomicOr(&s_bits[w >> 5], 1u << (w & 31)); }
             }
             if (bpsum > 0) {                                           // :884  bpsum ** 1.7 through the host libm's table
@@ -200,12 +165,8 @@ __device__ __forceinline__ void sq_prf_wave(const int16_t *refp, int known_n, co
         for (int k = 0; k < s.len; k++) tp += refp[s.i + k] == (int16_t)(s.j - k) ? 1 : 0;
     }
     tp = sq_wave_sum32(tp); np = sq_wave_sum32(np);
-    const int fp = np - tp, fn = known_n - tp;
     uint32_t inexact = 0;
-    m[0] = tp; m[1] = fp; m[2] = fn;
-    m[3] = (2 * tp + fp + fn) ? sq_round3(2.0 * tp / (double)(2 * tp + fp + fn), &inexact) : 1.0;
-    m[4] = (tp + fp) ? sq_round3((double)tp / (double)(tp + fp), &inexact) : 1.0;
-    m[5] = (tp + fn) ? sq_round3((double)tp / (double)(tp + fn), &inexact) : 1.0;
+    sq_prf_counts(tp, np, known_n, m, &inexact);
     if (inexact) *fallback = 1;
 }
 

@@ -196,6 +196,8 @@ class HipEngine:
         # max |M| of a shared stem matrix, remembered through a WEAK reference: the engine is process-wide and must not keep an
         # L x L device matrix (200 MB at L = 5000) alive after the alignment that owns it has ended
         self._sm_maxabs = (None, None)
+        #: score_tensors' table of (k / 2) ** 1.7, kept for the longest record seen (_pow17_table)
+        self._pow17 = None
 
     def fold_records(self, records, bpp=None, **opts):
         """records: list of (seq, reacts, restraints, dbn, paramsets, stemmatrix);
@@ -627,6 +629,76 @@ class HipEngine:
             raise RuntimeError("sq_align_pair_count: a pair table entry lies outside its record or the %d columns" % Lcols)
         assert n <= cap
         return flat[:n], count[:n], first[:n]
+
+    def score_tensors(self, recs, partner, row_start, row_rec):
+        """ScoreStruct, stems and metrics of given structures on the device (sq_score_structs_dev; SQRNdbnseq.py:958-970,
+        1249-1258).  recs: the records (score.ScoreRecord: prepared on the host once per record, however many rows it has);
+        partner: a flat int32 CUDA tensor of partner rows in input columns; row_start / row_rec: per row (host arrays) where
+        it starts in partner and its record.  Returns device tensors: scores float64[rows, 3], metrics float64[rows, 6],
+        status / npairs / nstems int32[rows], stems int32[S, 3], stem_off int64[rows + 1], ref_scores float64[records, 3],
+        ref_status int32[records].  No sq_batch.  Enqueued on the current stream; the one wait is for the number of stems,
+        which sizes their tensor."""
+        import torch
+        assert partner.is_cuda and partner.dtype == torch.int32 and partner.dim() == 1 and partner.is_contiguous()
+        L = _lib.load()
+        dev, R, rows = partner.device, len(recs), len(row_rec)
+        lens = np.array([rec.n for rec in recs], np.int64)
+        pos_off = np.zeros(R + 1, np.int64)
+        np.cumsum(lens, out=pos_off[1:])
+        cat = lambda parts, dt: np.concatenate([np.asarray(p, dt).reshape(-1) for p in parts] + [np.zeros(0, dt)])
+        has_reacts = np.array([rec.reacts is not None for rec in recs], np.uint8)
+        react_len = int(max((rec.n for rec in recs if rec.reacts is not None), default=0))
+        arrays = [pos_off, cat([rec.codes for rec in recs], np.uint8), has_reacts, np.array([rec.nsep for rec in recs], np.int32),
+                  cat([rec.known_partner for rec in recs], np.int32),
+                  np.array([len(rec.known) if rec.known is not None else -1 for rec in recs], np.int32),
+                  self._pow17_table(int(lens.max(initial=0))), np.asarray(row_start, np.int64).reshape(-1), np.asarray(row_rec, np.int32).reshape(-1)]
+        if react_len:
+            arrays.append(cat([np.asarray(rec.reacts, np.float64) if rec.reacts is not None else np.zeros(rec.n) for rec in recs], np.float64))
+        if rows:                                                     # (every row lies inside the tensor: the kernels trust it)
+            width = np.array([len(rec.seq) for rec in recs], np.int64)[arrays[8]]
+            assert int(arrays[7].min()) >= 0 and int((arrays[7] + width).max()) <= partner.numel(), "a row outside the partner tensor"
+        gaps = any(rec.has_gap for rec in recs)
+        if gaps:                                                     # (the maps between input columns and gap-free positions)
+            col_off = np.zeros(R + 1, np.int64)
+            np.cumsum([len(rec.colmap) for rec in recs], out=col_off[1:])
+            arrays += [col_off, cat([rec.colmap for rec in recs], np.int32), cat([rec.gfcol for rec in recs], np.int32)]
+        with torch.cuda.device(dev):
+            up = _upload_once([a if len(a) else np.zeros(1, a.dtype) for a in arrays], dev)
+            ptr = lambda t: C.c_void_p(t.data_ptr())
+            d = _lib.ScoreDesc(nrec=R, max_react_len=react_len, d_pos_off=ptr(up[0]), d_codes=ptr(up[1]), d_has_reacts=ptr(up[2]),
+                               d_nsep=ptr(up[3]), d_known=ptr(up[4]), d_known_n=ptr(up[5]), d_pow=ptr(up[6]), pow_len=len(arrays[6]),
+                               d_reacts=ptr(up[9]) if react_len else None)
+            if gaps:
+                d.d_col_off, d.d_colmap, d.d_gfcol = (ptr(t) for t in up[-3:])
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            out = dict(scores=new((rows, 3), torch.float64), metrics=new((rows, 6), torch.float64), status=new(rows, torch.int32),
+                       npairs=new(rows, torch.int32), nstems=new(rows, torch.int32), ref_scores=new((R, 3), torch.float64),
+                       ref_status=new(R, torch.int32))
+            nbytes = int(L.sq_score_scratch(R))
+            scratch = new(nbytes // 4, torch.int32)
+            stem_off = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
+            o = _lib.ScoreRows(nrows=rows, d_partner=ptr(partner), d_row_start=ptr(up[7]), d_row_rec=ptr(up[8]), d_status=ptr(out["status"]),
+                               d_npairs=ptr(out["npairs"]), d_nstems=ptr(out["nstems"]), d_stem_off=ptr(stem_off), d_stems=None, stem_cap=0,
+                               d_scores=ptr(out["scores"]), d_metrics=ptr(out["metrics"]), d_ref_scores=ptr(out["ref_scores"]),
+                               d_ref_status=ptr(out["ref_status"]))
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(L.sq_score_structs_dev(C.byref(d), C.byref(o), 0, ptr(scratch), nbytes, stream))
+            stem_off[1:] = torch.cumsum(out["nstems"], 0, dtype=torch.int64)
+            nstems = int(stem_off[-1].item())
+            out["stems"] = new((nstems, 3), torch.int32)
+            o.d_stems, o.stem_cap = (ptr(out["stems"]) if nstems else None), nstems
+            _lib.check(L.sq_score_structs_dev(C.byref(d), C.byref(o), 1, ptr(scratch), nbytes, stream))
+        out["stem_off"] = stem_off
+        return out
+
+    def _pow17_table(self, nmax):
+        """(k / 2) ** 1.7 for k <= 4 nmax with the host's pow, as ScoreStruct's `bpsum ** power` computes it (:884): a stem of
+        an n-nt record sums at most 4 x n / 2.  Kept for the longest record seen.  Python's float power IS the libm call the
+        reference makes; numpy's vectorised power may not be.  One pass of 4 n entries: ~20 ms once for a 32,768-nt record."""
+        have = self._pow17
+        if have is None or len(have) < 4 * nmax + 1:
+            have = self._pow17 = np.array([(0.5 * k) ** 1.7 for k in range(4 * max(nmax, 64) + 1)], np.float64)
+        return have[:4 * nmax + 1]
 
     def entropy(self, record, interchainonly=False):
         """Mean row entropy of the stem matrix under the FIRST paramset, as a string

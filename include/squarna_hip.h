@@ -534,6 +534,22 @@ SQ_API size_t sq_score_scratch(int32_t nrec);
 SQ_API int sq_score_structs_dev(const sq_score_desc *d, const sq_score_rows *o, int32_t pass, void *d_scratch, size_t scratch_bytes,
                                 void *hip_stream);
 
+/* ---- entropy mode as data (SQRNdbnseq.py:520-545, 1087-1089) ---------------------------------------------------------------
+ * sq_entropy_rows -- for each listed job: AnnotateStems with no selected stem; its stems (len >= minlen, bpscore >= minbpscore)
+ * form the symmetric N x N stem matrix, every cell (v, w) of a stem and its mirror holding the stem's total score; row i with
+ * S = sum_j m[i][j] != 0 has H_i = -sum_{j: m != 0} p log2 p, p = m[i][j] / S, in bits, else H_i = 0.  fp64 throughout.
+ * All d_ pointers are the caller's DEVICE memory: d_pos_off int64[njob + 1] -- list entry k's N values H_i are written to
+ * d_position[d_pos_off[k] ..] (d_pos_off[k + 1] - d_pos_off[k] must be N: rows beyond it are not written); d_mean[k] = sum_i
+ * H_i / N (NaN for N = 0); d_nstems[k] = the stems that formed the matrix.  d_scratch: sq_entropy_scratch(njob, cells) bytes,
+ * cells = the sum of N^2 over the list (one dense tile per entry); its content is undefined afterwards.
+ * Deterministic: a cell is stored by exactly one stem and every sum has one fixed order, so a job gives the same bits whatever
+ * else the call or the batch holds.  Sequences of more than 32,768 nt are refused (-1).
+ * Runs on the batch's stream like sq_align_accumulate; the outputs are complete when the call returns.  Returns 0, -1 (bad
+ * argument, scratch too small), -3 (a capacity of the batch: sq_last_capacity). */
+SQ_API size_t sq_entropy_scratch(int32_t njob, int64_t cells);
+SQ_API int sq_entropy_rows(sq_batch *b, int32_t njob, const int32_t *job_ids, const int64_t *d_pos_off, double *d_position,
+                           double *d_mean, int32_t *d_nstems, void *d_scratch, size_t scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -326,6 +326,22 @@ class Batch:
         _lib.check(self.L.sq_align_accumulate(self.h, pk.nseq, _ptr(ja), _ptr(pk.seq_off), _ptr(pk.cols), L,
                                               C.c_void_p(matrix.data_ptr())))
 
+    # -- entropy mode as data
+    def entropy_rows(self, jobs, pos_off, position, mean, nstems, scratch):
+        """The row entropies of the listed jobs' stem matrices (sq_entropy_rows; SQRNdbnseq.py:520-545): list entry k's N values
+        go to position[pos_off[k] ..], their mean to mean[k], the number of its stems to nstems[k].  pos_off int64[len(jobs) + 1],
+        position / mean float64, nstems int32, scratch uint8 (sq_entropy_scratch bytes for the jobs' N^2 cells): CUDA tensors of
+        the caller on the batch's device, complete on the batch's stream.  The results are complete when the call returns."""
+        torch = self.torch
+        assert pos_off.dtype == torch.int64 and pos_off.numel() == len(jobs) + 1 and nstems.dtype == torch.int32
+        assert position.dtype == torch.float64 and mean.dtype == torch.float64 and scratch.dtype == torch.uint8
+        assert all(t.is_cuda and t.is_contiguous() for t in (pos_off, position, mean, nstems, scratch))
+        assert mean.numel() >= len(jobs) and nstems.numel() >= len(jobs)
+        ja = np.array(jobs, np.int32)
+        _lib.check(self.L.sq_entropy_rows(self.h, len(jobs), _ptr(ja), C.c_void_p(pos_off.data_ptr()), C.c_void_p(position.data_ptr()),
+                                          C.c_void_p(mean.data_ptr()), C.c_void_p(nstems.data_ptr()), C.c_void_p(scratch.data_ptr()),
+                                          C.c_size_t(scratch.numel())))
+
     # -- a-8 / a-9 / Nussinov
     def run_algo(self, jobs, algo, levellimit=None, out_cap=1 << 16):
         """RunAlgo (SQRNdbnseq.py:548-595) for the listed jobs under 'E', 'H' or 'N':

@@ -55,9 +55,18 @@ struct ProfScope {
     }
 };
 
+struct SqEntropySink {                // mode 2 for sq_entropy_rows: per list entry k (sq_entropy_dev.hip)
+    const int64_t *h_tile_off;        // host [entries + 1]: entry k's N x N tile starts at d_tiles + h_tile_off[k]
+    const int64_t *d_tile_off;        // the same on the device
+    double *d_tiles;
+    const int64_t *d_pos_off;         // device [entries + 1]: entry k's N row entropies go to d_position + d_pos_off[k]
+    double *d_position, *d_mean;
+    int32_t *d_nstems;
+};
 struct AlignSink {                    // mode 2: where the stems of structure k of the list are added
     const int32_t *col_off, *cols;    // host: columns of list entry k are cols[col_off[k] .. col_off[k+1])
     int L; double *matrix;            // device L x L fp64
+    const SqEntropySink *ent = nullptr;   // set: no column matrix -- the entropy kernels read every entry's stems instead
 };
 
 // sq_host.hip
@@ -72,3 +81,7 @@ void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64
                              bool chained, bool pooled = false, const SqPoolRoundArgs *pool_round = nullptr);
 int sq_run_round_impl(sq_batch *b, SqLane &ln, const std::vector<SView> &structs, int mode,
                       std::vector<std::vector<HStem>> &out, const AlignSink *sink);
+
+// sq_entropy_dev.hip
+int sq_entropy_launch(sq_batch *b, hipStream_t st, const SqStruct *d_structs, const SqScanArgs &scan, int S, int first, int maxn,
+                      int64_t maxcap, const SqEntropySink &e);

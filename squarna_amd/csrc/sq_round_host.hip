@@ -368,7 +368,10 @@ static int run_chunk(sq_batch *b, SqLane &ln, const std::vector<SView> &structs,
     scan.ctr = ln.d_ctr;
     sq_launch_round_kernels(b, st, S, maxn, maxcap, need_reacts, scan_bytes, mode, io, scan, ln.d_structs, ln.d_strands, false);
     {
-        if (mode == 2) {
+        if (mode == 2 && sink->ent) {
+            // sq_entropy_rows: the survivor lists stay where they are; the entropy kernels read them behind the scoring kernel
+            if (int r = sq_entropy_launch(b, st, ln.d_structs, scan, S, (int)lo, maxn, maxcap, *sink->ent)) return r;
+        } else if (mode == 2) {
             // gap maps of the chunk's sequences into the (unused) round output buffer, then one scatter launch per
             // sequence, in list order: stream order == the reference's per-cell summation order (dbnali:233-237)
             int32_t *d_cols = (int32_t *)ln.d_out;

@@ -700,6 +700,78 @@ class HipEngine:
             have = self._pow17 = np.array([(0.5 * k) ** 1.7 for k in range(4 * max(nmax, 64) + 1)], np.float64)
         return have[:4 * nmax + 1]
 
+    def entropy_tensors(self, recs, interchainonly=False, M=1.8, B=-0.6, stem_matrix=None, bpp=None, scratch_bytes=None):
+        """Entropy mode as data (SQRNdbnseq.py:520-545, 1087-1089; sq_entropy_rows): recs = [(seq, reacts, restraints,
+        paramset)], one paramset (a dict) per record.  Returns device tensors in gap-free coordinates: position float64 -- the
+        row entropies H_i of record r's stem matrix from pos_off[r] on --, pos_off int64[R + 1], mean float64[R] (sum H_i / N;
+        NaN for a record without a position), nstems int32[R]; and the host array lengths int64[R].
+        stem_matrix: ONE L x L float64 CUDA tensor that weights the pair scores of every record through its gap map
+        (Batch(mul_shared=...): read where it is, never written); bpp: per record a CUDA float64 N x N tensor or None, for a
+        paramset with bpp != 0.  The records go through Batch in chunks whose dense N x N fp64 tiles fit scratch_bytes
+        (default 1 GiB; a larger record gets a chunk of its own); a chunk's kernels see its own tiles alone, so a record's
+        values do not depend on its chunk.  Nothing but sizes and offsets crosses PCIe."""
+        import torch
+        R = len(recs)
+        budget = int(scratch_bytes) if scratch_bytes else 1 << 30
+        prepared = [Prepared(r[0], r[1], r[2], None) for r in recs]
+        lens = np.array([len(p.shortseq) for p in prepared], np.int64)
+        if R and int(lens.max()) > 32768:
+            k = int(lens.argmax())
+            raise ValueError("entropy_tensors: record %d has %d nt; at most 32768 are supported" % (k, lens[k]))
+        pos_off = np.zeros(R + 1, np.int64)
+        np.cumsum(lens, out=pos_off[1:])
+        dev = torch.device("cuda", torch.cuda.current_device())
+        L = _lib.load()
+        lists = {}                                                   # (one list object per paramset: records that share it share the batch's job table)
+        psets = [lists.setdefault(id(r[3]), [r[3]]) for r in recs]
+        maxabs = None
+        if stem_matrix is not None:
+            assert stem_matrix.is_cuda and stem_matrix.dtype == torch.float64 and stem_matrix.dim() == 2 and stem_matrix.is_contiguous()
+            maxabs = float(stem_matrix.abs().max().item()) if stem_matrix.numel() else 0.0
+        live = [k for k in range(R) if lens[k] > 0]                  # (a record without a position: no job, no row, mean NaN)
+        chunks, lo = [], 0
+        while lo < len(live):
+            hi, cells = lo, 0
+            while hi < len(live) and (hi == lo or int(L.sq_entropy_scratch(hi - lo + 1, cells + int(lens[live[hi]]) ** 2)) <= budget):
+                cells += int(lens[live[hi]]) ** 2
+                hi += 1
+            chunks.append((live[lo:hi], int(L.sq_entropy_scratch(hi - lo, cells))))
+            lo = hi
+        with torch.cuda.device(dev):
+            position = torch.empty(max(int(pos_off[-1]), 1), dtype=torch.float64, device=dev)[:int(pos_off[-1])]
+            mean = torch.full((R,), float("nan"), dtype=torch.float64, device=dev)
+            nstems = torch.zeros(R, dtype=torch.int32, device=dev)
+            scratch = torch.empty(max((nb for _, nb in chunks), default=0), dtype=torch.uint8, device=dev)
+            for idx, nbytes in chunks:
+                chunk = [prepared[k] for k in idx]
+                cpsets = [psets[k] for k in idx]
+                terms, bpp_dev = bpp_terms(chunk, cpsets, M, B, given=[bpp[k] if bpp is not None else None for k in idx], device=True)
+                mul_shared = None
+                if stem_matrix is not None:
+                    mul_shared = (stem_matrix, [np.flatnonzero(~gap_mask(recs[k][0])).astype(np.int32) for k in idx], maxabs)
+                d_off, = _upload_once([np.append(pos_off[idx], pos_off[idx[-1] + 1])], dev)
+                cmean = torch.empty(len(idx), dtype=torch.float64, device=dev)
+                cnst = torch.empty(len(idx), dtype=torch.int32, device=dev)
+                cand = max(self.cand_per_nt, 64)
+                for attempt in range(4):
+                    try:
+                        with Batch(chunk, cpsets, interchainonly=interchainonly, max_structs=self.max_structs, cand_per_nt=cand,
+                                   fp32=False, bpp=terms, bpp_dev=bpp_dev, mul_shared=mul_shared) as b:
+                            b.entropy_rows(list(range(len(idx))), d_off, position, cmean, cnst, scratch[:nbytes])
+                        break
+                    except _lib.CapacityError as e:
+                        # more maximal runs than the candidate records were sized for (GC-only records, minlen 1): the chunk
+                        # again with four times as many, as fold_records does
+                        if e.kind != _lib.CAP_CANDIDATES or attempt == 3:
+                            raise
+                        runs = max(0.375 ** (max(1.0, float(np.ceil(pl[0]["minlen"]))) - 1.0) for pl in cpsets)
+                        cand = int(max(cand, 0.117 * 1.6 * int(lens[idx].max()) * runs) * 4) + 1
+                        self.capacity_retries += 1
+                at = torch.from_numpy(np.asarray(idx, np.int64)).to(dev)
+                mean[at], nstems[at] = cmean, cnst
+            d_pos_off, = _upload_once([pos_off], dev)
+        return dict(position=position, pos_off=d_pos_off, mean=mean, nstems=nstems, lengths=lens)
+
     def entropy(self, record, interchainonly=False):
         """Mean row entropy of the stem matrix under the FIRST paramset, as a string
         (SQRNdbnseq.py:520-545, 1087-1089); the stems come from the GPU scan (mode 1)."""

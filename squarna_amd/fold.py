@@ -226,6 +226,69 @@ def _join(parts, seqs):
                 cell_off=torch.from_numpy(cell_off).to(dev)), nstruct, out_len
 
 
+def _pick(cur, *alts):
+    """A keyword's value: the last of its synonyms that was given, else the keyword itself."""
+    for alt in alts:
+        if alt is not None:
+            cur = alt
+    return cur
+
+
+def _check_sources(records, inputfile, inputseq, fileformat, configfile, inputformat, HOME_DIR, priority):
+    """Predict's checks of where the input and the configuration come from, same messages (SQUARNA.py:677-703):
+    (inputfile, configfile, whether the caller named one, priority names, HOME_DIR)."""
+    if HOME_DIR is None:
+        HOME_DIR = DATA_DIR
+    if inputfile != None and not os.path.exists(inputfile) and os.path.exists(os.path.join(HOME_DIR, inputfile)):
+        inputfile = os.path.join(HOME_DIR, inputfile)
+    assert records is not None or os.path.exists(str(inputfile)) or inputseq, "Input file does not exist."
+    assert fileformat in {'unknown', 'fasta', 'default', 'stockholm', 'clustal'}, \
+        "Wrong fileformat, choose one of these: default,fasta,stockholm,clustal"
+    configfile, configfileset, priority = _api._find_config(configfile, HOME_DIR, priority)
+    assert ''.join(sorted(inputformat.replace('x', ''))) in {"q", "fq", "qr", "qt", "qrt", "fqr", "fqt", "fqrt"}, \
+        'Inappropriate inputformat value (subset of "fqrtx" with "q" being mandatory): {}'.format(inputformat)
+    return inputfile, configfile, configfileset, priority, HOME_DIR
+
+
+def _as_float(value, what):
+    try:
+        return float(value)
+    except Exception:
+        raise ValueError("Inappropriate {} value (float): {}".format(what, value))
+
+
+def _configs_by_length(configfile, configfileset, HOME_DIR, maxstemnum=None):
+    """config_for(sequence) -> (paramset names, paramsets): the named configuration, or by length def / 500 / 1000
+    (autoconfig, SQUARNA.py:868-878)."""
+    configs = [ParseConfig(configfile)]
+    if not configfileset:
+        configs += [ParseConfig(os.path.join(HOME_DIR, "500.conf")), ParseConfig(os.path.join(HOME_DIR, "1000.conf"))]
+    if maxstemnum is not None:
+        for _, group in configs:
+            for ps in group:
+                ps['maxstemnum'] = maxstemnum
+
+    def config_for(sequence):
+        if configfileset or len(sequence) < 500:
+            return configs[0]
+        return configs[2] if len(sequence) >= 1000 else configs[1]
+    return config_for
+
+
+def _input_records(records, inputseq, inputfile, inputformat, fileformat, ignorewarn, inputrestr, M, B):
+    """The (name, sequence, reactivities, restraints, reference) tuples of `records` or of the parsed input."""
+    if records is not None:
+        inputs = [(">record{}".format(k + 1), rec, None, None, None) if isinstance(rec, str) else tuple(rec)
+                  for k, rec in enumerate(records)]
+        assert all(len(rec) == 5 for rec in inputs), "records: sequences or (name, sequence, reactivities, restraints, reference)"
+    else:
+        with contextlib.redirect_stdout(io.StringIO()):          # (the parser announces a guessed file format)
+            inputs = list(ParseInput(inputseq, inputfile, inputformat, fmt=fileformat, ignore=ignorewarn,
+                                     inputrestr=inputrestr, M=M, B=B)[0])
+    assert inputs, "No input records."
+    return inputs
+
+
 def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, inputformat="qtrf", maxstemnum=None,
          algorithms='', rankby="r", hardrest=False, interchainonly=False, toplim=5, outplim=None, conslim=1, poollim=1000,
          levellimit=None, ignorewarn=False, HOME_DIR=None, priority=None, M=1.8, B=-0.6, records=None,
@@ -250,11 +313,7 @@ def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, i
     their device; CPU tensors and arrays are uploaded once per record, not once per paramset.  The tensors are not modified.
     With an engine without ``fold_tensors`` the matrices go through the provider hook (``set_bpp_provider``) instead; records
     with the same sequence must then carry the same matrix."""
-    def pick(cur, *alts):
-        for alt in alts:
-            if alt is not None:
-                cur = alt
-        return cur
+    pick = _pick
     inputfile = pick(inputfile, i); fileformat = pick(fileformat, ff)
     configfile = pick(configfile, config, c); inputseq = pick(inputseq, seq, s)
     algorithms = pick(algorithms, algorithm, algo); rankby = pick(rankby, rb)
@@ -267,29 +326,12 @@ def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, i
         if flag:
             raise ValueError("Fold does not cover {}: use Predict".format(what))
 
-    if HOME_DIR is None:
-        HOME_DIR = DATA_DIR
-    if inputfile != None and not os.path.exists(inputfile) and os.path.exists(os.path.join(HOME_DIR, inputfile)):
-        inputfile = os.path.join(HOME_DIR, inputfile)
-
     # ---- validation: Predict's checks of the keywords both take, same messages (SQUARNA.py:677-808)
-    assert records is not None or os.path.exists(str(inputfile)) or inputseq, "Input file does not exist."
-    assert fileformat in {'unknown', 'fasta', 'default', 'stockholm', 'clustal'}, \
-        "Wrong fileformat, choose one of these: default,fasta,stockholm,clustal"
-    configfile, configfileset, priority = _api._find_config(configfile, HOME_DIR, priority)
-    assert ''.join(sorted(inputformat.replace('x', ''))) in {"q", "fq", "qr", "qt", "qrt", "fqr", "fqt", "fqrt"}, \
-        'Inappropriate inputformat value (subset of "fqrtx" with "q" being mandatory): {}'.format(inputformat)
-
+    inputfile, configfile, configfileset, priority, HOME_DIR = _check_sources(records, inputfile, inputseq, fileformat, configfile,
+                                                                              inputformat, HOME_DIR, priority)
     if maxstemnum is not None:
         maxstemnum = _api._as_int(maxstemnum, "maxstemnum", lambda x: x >= 0, "non-negative integer")
-    try:
-        M = float(M)
-    except Exception:
-        raise ValueError("Inappropriate M value (float): {}".format(M))
-    try:
-        B = float(B)
-    except Exception:
-        raise ValueError("Inappropriate B value (float): {}".format(B))
+    M, B = _as_float(M, "M"), _as_float(B, "B")
     try:
         algos = set(algorithms.upper())
         assert algos <= {'E', 'G', 'H', 'N'}
@@ -310,28 +352,8 @@ def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, i
             raise ValueError("Inappropriate levellimit value (integer): {}".format(levellimit))
     rankbydiff, rankby = _api._rank_keys(rankby)
 
-    configs = [ParseConfig(configfile)]
-    if not configfileset:                                        # autoconfig, SQUARNA.py:868-878
-        configs += [ParseConfig(os.path.join(HOME_DIR, "500.conf")), ParseConfig(os.path.join(HOME_DIR, "1000.conf"))]
-    if maxstemnum is not None:
-        for _, group in configs:
-            for ps in group:
-                ps['maxstemnum'] = maxstemnum
-
-    def config_for(sequence):
-        if configfileset or len(sequence) < 500:
-            return configs[0]
-        return configs[2] if len(sequence) >= 1000 else configs[1]
-
-    if records is not None:
-        inputs = [(">record{}".format(k + 1), rec, None, None, None) if isinstance(rec, str) else tuple(rec)
-                  for k, rec in enumerate(records)]
-        assert all(len(rec) == 5 for rec in inputs), "records: sequences or (name, sequence, reactivities, restraints, reference)"
-    else:
-        with contextlib.redirect_stdout(io.StringIO()):          # (the parser announces a guessed file format)
-            inputs = list(ParseInput(inputseq, inputfile, inputformat, fmt=fileformat, ignore=ignorewarn,
-                                     inputrestr=inputrestr, M=M, B=B)[0])
-    assert inputs, "No input records."
+    config_for = _configs_by_length(configfile, configfileset, HOME_DIR, maxstemnum)
+    inputs = _input_records(records, inputseq, inputfile, inputformat, fileformat, ignorewarn, inputrestr, M, B)
 
     eng = _engine.get_engine()
     keep = max(int(outplim), 1)

@@ -467,6 +467,22 @@ SQ_API size_t sq_first_fit_scratch(int64_t n, int32_t L);
 SQ_API int sq_first_fit_dev(const int64_t *d_flat, int64_t n, int32_t L, int32_t minspan, int32_t *d_partner, void *d_scratch,
                             size_t scratch_bytes, int32_t *d_info, void *hip_stream);
 
+/* ---- pair counts over sliding windows (FoldWindows) ---------------------------------------------------
+ * The windows of long sequences lie on one axis of Ltot (<= 2^31 - 1) positions on which the records follow one another:
+ * window k covers [d_start[k], d_start[k] + d_len[k]), d_start int64[nwin] non-decreasing (so are the ends), and its
+ * structure is row 0 of record rec0 + k of the pair tables d_partner / d_cell_off (sq_result_pairs_dev's layout; d_cell_off
+ * holds at least rec0 + nwin + 1 offsets), in the window's own coordinates.  For every distinct pair gi < gj of axis positions
+ * that any window's row holds, one record is written, unordered: d_flat = gi * Ltot + gj, d_count = the windows that hold
+ * the pair, d_cover = the windows that contain both positions, d_first = the smallest k of a holder.  The first holder
+ * forms the record from its neighbours' rows (csrc/sq_windows.h): no dense table, no scratch, no atomics on data.
+ * d_out[0] = the number of distinct pairs (may exceed cap: then only cap were stored and nothing is written beyond cap),
+ * d_out[1] = 0, or 2 when an entry was invalid -- a partner outside [-1, len), the position itself or one that does not
+ * point back, a window outside the axis or longer than its table -- (such an entry is not counted).
+ * Asynchronous on hip_stream, allocates nothing; 0, or -1 (bad argument: nothing enqueued). */
+SQ_API int sq_window_pair_count(const int32_t *d_partner, const int64_t *d_cell_off, int32_t rec0, int32_t nwin, const int64_t *d_start,
+                                const int32_t *d_len, int64_t Ltot, int64_t *d_flat, int32_t *d_count, int32_t *d_cover,
+                                int32_t *d_first, int64_t cap, uint64_t *d_out, void *hip_stream);
+
 /* ---- measurement ------------------------------------------------------------
  * Kernel ids: 0 fill, 1 state, 2 stem_scan, 3 stem_score (+ select), 4 Edmonds, 5 Hungarian,
  * 6 Nussinov, 9 the bpp terms formed at sq_batch_create from bpp_matrix_dev (both kernels; recorded whether profiling

@@ -630,6 +630,40 @@ class HipEngine:
         assert n <= cap
         return flat[:n], count[:n], first[:n]
 
+    def window_pair_count(self, partner, cell_off, rec0, starts, lens, Ltot, cap=None):
+        """The pair table of sliding windows on the device (sq_window_pair_count): partner / cell_off = pair tables in
+        fold_tensors' layout, window k = record rec0 + k (its consensus row, in the window's own coordinates); starts int64
+        (non-decreasing, on the axis of Ltot positions on which the records follow one another) and lens int32: device
+        tensors.  Returns the device tensors (flat int64 = gi * Ltot + gj, count, cover, first int32) of the distinct
+        pairs, unordered.  `cap` (default 1 << 16) sizes the result buffers; the call is repeated with the true number when
+        it was too small (matrix_select's protocol).  Only that number comes to the host."""
+        import torch
+        L = _lib.load()
+        dev, nwin = partner.device, int(starts.numel())
+        assert starts.dtype == torch.int64 and lens.dtype == torch.int32 and int(lens.numel()) == nwin
+        assert partner.dtype == torch.int32 and cell_off.dtype == torch.int64 and int(cell_off.numel()) >= int(rec0) + nwin + 1
+        starts, lens = starts.contiguous(), lens.contiguous()
+        cap = 1 << 16 if cap is None else int(cap)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            while True:
+                flat = torch.empty(cap, dtype=torch.int64, device=dev)
+                count, cover, first = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
+                out = torch.empty(2, dtype=torch.int64, device=dev)
+                _lib.check(L.sq_window_pair_count(C.c_void_p(partner.data_ptr()), C.c_void_p(cell_off.data_ptr()), int(rec0), nwin,
+                                                  C.c_void_p(starts.data_ptr()), C.c_void_p(lens.data_ptr()), int(Ltot),
+                                                  C.c_void_p(flat.data_ptr()), C.c_void_p(count.data_ptr()),
+                                                  C.c_void_p(cover.data_ptr()), C.c_void_p(first.data_ptr()), cap,
+                                                  C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)))
+                n, status = out.tolist()
+                if status:
+                    raise RuntimeError("sq_window_pair_count: a pair table entry is not a pair inside its window, or a window "
+                                       "lies outside the %d positions or its table" % Ltot)
+                if n <= cap:
+                    break
+                cap = n
+        return flat[:n], count[:n], cover[:n], first[:n]
+
     def score_tensors(self, recs, partner, row_start, row_rec):
         """ScoreStruct, stems and metrics of given structures on the device (sq_score_structs_dev; SQRNdbnseq.py:958-970,
         1249-1258).  recs: the records (score.ScoreRecord: prepared on the host once per record, however many rows it has);

@@ -122,7 +122,8 @@ def _cells_of(stems, matrix, N, value):
 def Edmonds(stems, power=1.7, matrix=None):
     """Maximum-weight matching of the stem cells -- SQRNalgos.py:96-110.  networkx.max_weight_matching restated
     step by step on the GPU (sq_mwm): same pairs, same (u, v) orientation, same sorted order as the reference
-    returns, including which of several optimal matchings is found."""
+    returns, including which of several optimal matchings is found.  One graph per call here; the C entry takes `ngraph`
+    graphs per call (include/squarna_hip.h) -- tests/matching_checks.py (mwm_many) is the example of calling it so."""
     from . import _lib
     import ctypes as C
     L = _lib.load()
@@ -147,7 +148,8 @@ def Edmonds(stems, power=1.7, matrix=None):
 def Hungarian(seq, stems, N, seps, minloop=3, power=1.7, matrix=None):
     """Linear-sum-assignment matching of the stem cells -- SQRNalgos.py:113-135.  scipy's
     linear_sum_assignment restated step by step on the GPU (sq_lsap); the mutual-pair filter (:130-133) is
-    O(N) host work."""
+    O(N) host work.  One matrix per call here; the C entry takes `nprob` matrices per call (include/squarna_hip.h) --
+    tests/matching_checks.py (lsap_many) is the example of calling it so."""
     from . import _lib
     import ctypes as C
     L = _lib.load()
@@ -184,7 +186,9 @@ def Hungarian(seq, stems, N, seps, minloop=3, power=1.7, matrix=None):
 
 
 def Nussinov(seq, stems, N, seps, minloop=3, matrix=None):
-    """Nussinov DP over the stem cells + BackTrack -- SQRNalgos.py:44-93, on the GPU (sq_nussinov)."""
+    """Nussinov DP over the stem cells + BackTrack -- SQRNalgos.py:44-93, on the GPU (sq_nussinov).  One sequence per call
+    here; the C entry takes `nprob` sequences per call (include/squarna_hip.h) -- tests/matching_checks.py (nussinov_many)
+    is the example of calling it so."""
     from . import _lib
     from .dbn import encode_seq
     import ctypes as C

@@ -78,6 +78,7 @@ int build_cells(int32_t nprob, const int32_t *n, const int64_t *cell_off, const 
         if (cell_off[g + 1] < cell_off[g]) { sq_set_error("cell_off must be non-decreasing"); return -1; }
         SqMatchJob &J = C.jobs[g];
         J.n = n[g]; J.edge_off = (int64_t)C.edges.size(); J.pos_off = (int64_t)C.ncodes; C.ncodes += (size_t)n[g];
+        J.pad = g;                       // run_matching hands the kernels a writable table: sq_nussinov_kernel files the count under pad
         std::unordered_map<uint64_t, size_t> seen;
         for (int64_t e = cell_off[g]; e < cell_off[g + 1]; e++) {
             int32_t a = cv[e], b = cw[e];

@@ -10,6 +10,7 @@
 // All buffers are the caller's device memory, everything is enqueued on the caller's stream, nothing is allocated or waited for.
 #include "sq_host_int.h"
 #include "sq_firstfit.h"
+#include "sq_emit.h"
 
 // ---- lift and count -----------------------------------------------------------------------------------------------------
 // One thread per (row r, gap-free position i): the pair (i, j = partner) with i < j becomes the column pair (v, w).  A row
@@ -36,29 +37,19 @@ extern "C" __global__ __launch_bounds__(256) void sq_pair_count_kernel(const int
     }
 }
 
-// The cells of the upper triangle with count >= threshold, staged in LDS and written out behind one atomic per thousand
-// (sq_colselect_kernel's form).  Unordered.
+// The cells of the upper triangle with count >= threshold, through the block's emission stage (sq_emit.h): staged in LDS and
+// written out behind one atomic per thousand.  Unordered.
 extern "C" __global__ __launch_bounds__(256) void sq_pair_select_kernel(const int32_t *count, const int32_t *first, int L, int threshold,
                                                                         long long *flat_out, int32_t *count_out, int32_t *first_out,
                                                                         long long cap, unsigned long long *out)
 {
-    __shared__ long long s_flat[1024];
-    __shared__ int32_t s_cnt[1024], s_first[1024];
-    __shared__ uint32_t s_n;
-    __shared__ unsigned long long s_base;
-    const int tid = threadIdx.x, lane = tid & 63;
-    if (tid == 0) s_n = 0u;
-    __syncthreads();
-    auto flush = [&]() {                                    // (block-uniform call, between barriers)
-        const uint32_t n = s_n;
-        if (tid == 0) s_base = atomicAdd(out, (unsigned long long)n);
-        __syncthreads();
-        const unsigned long long base = s_base;
-        for (uint32_t k = tid; k < n; k += 256)
-            if ((long long)(base + k) < cap) { flat_out[base + k] = s_flat[k]; count_out[base + k] = s_cnt[k]; first_out[base + k] = s_first[k]; }
-        __syncthreads();
-        if (tid == 0) s_n = 0u;
-        __syncthreads();
+    __shared__ long long s_flat[SQ_EMIT_STAGE];
+    __shared__ int32_t s_cnt[SQ_EMIT_STAGE], s_first[SQ_EMIT_STAGE];
+    __shared__ SqEmitStage em;
+    const int tid = threadIdx.x;
+    em.init();
+    auto write = [&](uint32_t k, unsigned long long at) {
+        if ((long long)at < cap) { flat_out[at] = s_flat[k]; count_out[at] = s_cnt[k]; first_out[at] = s_first[k]; }
     };
     for (int v = blockIdx.x; v < L; v += gridDim.x) {
         const int32_t *row = count + (int64_t)v * L;
@@ -66,21 +57,12 @@ extern "C" __global__ __launch_bounds__(256) void sq_pair_select_kernel(const in
             const int w = wb + tid;
             const int32_t c = w < L ? row[w] : 0;
             const bool hit = c >= threshold;
-            const unsigned long long m = __ballot(hit);
-            if (m != 0ull) {
-                uint32_t b0 = 0u;
-                if (lane == 0) b0 = atomicAdd(&s_n, (uint32_t)__popcll(m));
-                b0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)b0);
-                if (hit) {
-                    const uint32_t at = b0 + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                    s_flat[at] = (int64_t)v * L + w; s_cnt[at] = c; s_first[at] = first[(int64_t)v * L + w];
-                }
-            }
-            __syncthreads();
-            if (s_n > 768u) flush();                         // (room for the next 256)
+            const uint32_t at = em.slot(hit);
+            if (hit) { s_flat[at] = (int64_t)v * L + w; s_cnt[at] = c; s_first[at] = first[(int64_t)v * L + w]; }
+            em.step(out, write);
         }
     }
-    if (s_n > 0u) flush();
+    em.finish(out, write);
 }
 
 extern "C" size_t sq_align_pair_count_scratch(int32_t L)

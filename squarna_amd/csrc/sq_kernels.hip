@@ -20,6 +20,7 @@
 
 #include "sq_cells.h"
 #include "sq_context.h"
+#include "sq_emit.h"
 
 // ------------------------------------------------------------------------------------
 // a-1  fill: one thread = 4 consecutive floats of the padded N x ld matrix (16-byte stores)
@@ -1234,25 +1235,15 @@ extern "C" __global__ __launch_bounds__(256) void sq_colselect_kernel(const doub
                                                                      long long *idx_out, double *val_out, long long cap,
                                                                      unsigned long long *count)
 {
-    // A block takes rows blockIdx.x, + gridDim.x, ...; the cells it selects are staged in LDS and written out a thousand at a time
-    // behind ONE atomic on the counter.  (Iteration 1 of a conserved alignment selects hundreds of thousands of cells: an atomic
-    // per cell -- and, tried first in round 6, per wave -- on one address was the kernel's whole 1.8 ms for 100 MB of reads.)
-    __shared__ long long s_idx[1024];
-    __shared__ double s_val[1024];
-    __shared__ uint32_t s_n;
-    __shared__ unsigned long long s_base;
-    const int tid = threadIdx.x, lane = tid & 63;
-    if (tid == 0) s_n = 0u;
-    __syncthreads();
-    auto flush = [&]() {                                    // (block-uniform call, between barriers)
-        const uint32_t n = s_n;
-        if (tid == 0) s_base = atomicAdd(count, (unsigned long long)n);
-        __syncthreads();
-        const unsigned long long base = s_base;
-        for (uint32_t k = tid; k < n; k += 256) if ((long long)(base + k) < cap) { idx_out[base + k] = s_idx[k]; val_out[base + k] = s_val[k]; }
-        __syncthreads();
-        if (tid == 0) s_n = 0u;
-        __syncthreads();
+    // A block takes rows blockIdx.x, + gridDim.x, ...; the cells it selects go through the block's emission stage (sq_emit.h):
+    // staged in LDS, written out a thousand at a time behind ONE atomic on the counter.
+    __shared__ long long s_idx[SQ_EMIT_STAGE];
+    __shared__ double s_val[SQ_EMIT_STAGE];
+    __shared__ SqEmitStage em;
+    const int tid = threadIdx.x;
+    em.init();
+    auto write = [&](uint32_t k, unsigned long long at) {
+        if ((long long)at < cap) { idx_out[at] = s_idx[k]; val_out[at] = s_val[k]; }
     };
     for (int v = blockIdx.x; v < L; v += gridDim.x) {
         const double *row = matrix + (int64_t)v * L;
@@ -1260,16 +1251,10 @@ extern "C" __global__ __launch_bounds__(256) void sq_colselect_kernel(const doub
             const int w = wb + tid;
             const double x = w < L ? row[w] : 0.0;
             const bool hit = w < L && x >= thr;
-            const unsigned long long m = __ballot(hit);
-            if (m != 0ull) {
-                uint32_t b0 = 0u;
-                if (lane == 0) b0 = atomicAdd(&s_n, (uint32_t)__popcll(m));
-                b0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)b0);
-                if (hit) { const uint32_t at = b0 + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); s_idx[at] = (int64_t)v * L + w; s_val[at] = x; }
-            }
-            __syncthreads();
-            if (s_n > 768u) flush();                         // (room for the next 256)
+            const uint32_t at = em.slot(hit);
+            if (hit) { s_idx[at] = (int64_t)v * L + w; s_val[at] = x; }
+            em.step(count, write);
         }
     }
-    if (s_n > 0u) flush();
+    em.finish(count, write);
 }

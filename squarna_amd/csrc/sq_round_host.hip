@@ -632,8 +632,6 @@ extern "C" int sq_colmatrix_select(const double *d_matrix, int32_t L, double thr
     if (!d_matrix || L <= 0 || cap < 0 || !d_count || (cap && (!d_idx || !d_val))) { sq_set_error("bad argument"); return -1; }
     hipStream_t st = (hipStream_t)hip_stream;
     HIPCK(hipMemsetAsync(d_count, 0, 8, st));
-    const int64_t total = (int64_t)L * L;
-    (void)total;
     hipLaunchKernelGGL(sq_colselect_kernel, dim3((unsigned)std::min<int32_t>(L, 2048)), dim3(256), 0, st,
                        d_matrix, L, threshold, minspan, (long long *)d_idx, d_val, (long long)cap, (unsigned long long *)d_count);
     return sq_check(hipGetLastError(), "sq_colselect_kernel");

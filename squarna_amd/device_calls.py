@@ -1,0 +1,226 @@
+"""The batch-free device entries of libsquarna_hip.so: calls that take the caller's device tensors, enqueue on the current
+stream and own no sq_batch -- the select / count / first-fit steps of alignment mode and of sliding windows, and the scoring
+of given structures.  HipEngine (engine.py) inherits them; engine.py itself keeps batching and the fold / retry machinery.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+
+def _ptr(t):
+    """The address of a device tensor as the C ABI takes it (None: a null pointer)."""
+    return C.c_void_p(t.data_ptr() if t is not None else None)
+
+
+def _stream(device):
+    """torch's current stream on `device`, as the C ABI takes it."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _upload_once(arrays, device):
+    """The numpy arrays as torch tensors on `device`, through ONE host-to-device copy (every array starts 8-byte aligned)."""
+    import torch
+    offs, total = [], 0
+    for a in arrays:
+        offs.append(total)
+        total += (a.nbytes + 7) & ~7
+    host = np.zeros(max(total, 8), np.uint8)
+    for a, o in zip(arrays, offs):
+        host[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    dev = torch.from_numpy(host).to(device)
+    return [dev[o:o + a.nbytes].view(getattr(torch, a.dtype.name)).reshape(a.shape) for a, o in zip(arrays, offs)]
+
+
+def _call_until_fits(device, cap, dtypes, call, status_error):
+    """The protocol of the entries that emit a number of records nobody knows beforehand (sq_colmatrix_select,
+    sq_window_pair_count): result tensors of `cap` entries, one per dtype, are allocated on `device`; call(tensors, cap, out)
+    enqueues the entry, which leaves (records, status) in the two int64 words of `out` -- it counts every record, also those
+    beyond cap; the two words are read once.  RuntimeError(status_error) on a status; the call is repeated once, with cap =
+    the true number, when that was larger.  Returns the tensors cut to the records' number: only that number comes to the
+    host."""
+    import torch
+    while True:                                                    # result buffers are torch tensors (caller-owned)
+        tensors = [torch.empty(cap, dtype=dt, device=device) for dt in dtypes]
+        out = torch.zeros(2, dtype=torch.int64, device=device)
+        call(tensors, cap, out)
+        n, status = out.tolist()
+        if status:
+            raise RuntimeError(status_error)
+        if n <= cap:
+            return tuple(t[:n] for t in tensors)
+        cap = n
+
+
+class DeviceCalls:
+    """The engine's batch-free device methods (mixed into HipEngine)."""
+    #: score_tensors' table of (k / 2) ** 1.7, kept for the longest record seen (_pow17_table)
+    _pow17 = None
+
+    def matrix_select(self, matrix, threshold, minspan=4):
+        """Device tensors (flat indices int64, values float64) of the upper cells >= threshold with span >= minspan of a
+        device matrix, unordered (sq_colmatrix_select); only the cells' number comes to the host."""
+        import torch
+        Lcols, dev = int(matrix.shape[0]), matrix.device
+
+        def call(res, cap, out):                                   # (the entry has no status: out[1] stays 0)
+            _lib.check(_lib.load().sq_colmatrix_select(_ptr(matrix), Lcols, float(threshold), int(minspan), _ptr(res[0]), _ptr(res[1]),
+                                                       cap, _ptr(out), _stream(dev)))
+
+        return _call_until_fits(dev, 1 << 16, (torch.int64, torch.float64), call, None)
+
+    def matrix_cells(self, matrix, threshold, minspan=4, sort=True):
+        """(flat indices, values) of the upper cells >= threshold with span >= minspan of a device matrix,
+        sorted by flat index unless sort=False (MatrixToDBNs' candidates, SQRNdbnali.py:127-148)."""
+        idx, val = self.matrix_select(matrix, threshold, minspan)
+        idx, val = idx.cpu().numpy(), val.cpu().numpy()
+        if not sort:
+            return idx, val
+        order = np.argsort(idx, kind="stable")
+        return idx[order], val[order]
+
+    def first_fit(self, flat, Lcols, minspan=0):
+        """The greedy pass over ranked candidates on the device (sq_first_fit_dev): flat = int64 device tensor of cells
+        v * Lcols + w in rank order; a candidate of span >= minspan joins iff both of its columns are still free
+        (MatrixToDBNs' first structure SQRNdbnali.py:127-192 with minspan 4, Consensus :285-295 with none).  Returns
+        (partner int32[Lcols] on the device, -1 where free; info int32[4] on the device: status, rounds, pairs, live).
+        Enqueued on the current stream; nothing is waited for."""
+        import torch
+        flat = flat.contiguous()
+        assert flat.dtype == torch.int64 and flat.is_cuda and flat.dim() == 1
+        L = _lib.load()
+        n, dev = int(flat.numel()), flat.device
+        with torch.cuda.device(dev):
+            nbytes = int(L.sq_first_fit_scratch(n, int(Lcols)))
+            scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+            partner = torch.empty(int(Lcols), dtype=torch.int32, device=dev)
+            info = torch.empty(4, dtype=torch.int32, device=dev)
+            _lib.check(L.sq_first_fit_dev(_ptr(flat if n else None), n, int(Lcols), int(minspan), _ptr(partner), _ptr(scratch), nbytes,
+                                          _ptr(info), _stream(dev)))
+        return partner, info
+
+    def align_pair_count(self, partner, cell_off, gap_maps, Lcols, threshold=1):
+        """Consensus' dict on the device (sq_align_pair_count): partner / cell_off = the pair tables of fold_tensors (gap-free
+        coordinates), gap_maps = per record the int32 array of its positions' alignment columns.  Returns the device
+        tensors (flat int64 = v * Lcols + w, count int32, first int32) of the distinct column pairs that at least
+        `threshold` records' consensus rows hold, unordered; only their number comes to the host."""
+        import torch
+        L = _lib.load()
+        dev, nrec = partner.device, len(gap_maps)
+        col_off = np.zeros(nrec + 1, np.int32)
+        np.cumsum([len(g) for g in gap_maps], out=col_off[1:])
+        cols = np.concatenate(gap_maps).astype(np.int32) if nrec else np.zeros(0, np.int32)
+        assert int(cell_off.numel()) == nrec + 1
+        cap = max(int(col_off[-1]) // 2, 1)                          # (a record of n positions holds at most n / 2 pairs)
+        with torch.cuda.device(dev):
+            if not partner.numel():                                  # (every row all gaps: no table, no pair)
+                return tuple(torch.empty(0, dtype=dt, device=dev) for dt in (torch.int64, torch.int32, torch.int32))
+            d_off, d_cols = _upload_once([col_off, cols if len(cols) else np.zeros(1, np.int32)], dev)
+            nbytes = int(L.sq_align_pair_count_scratch(int(Lcols)))
+            scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+            flat = torch.empty(cap, dtype=torch.int64, device=dev)
+            count = torch.empty(cap, dtype=torch.int32, device=dev)
+            first = torch.empty(cap, dtype=torch.int32, device=dev)
+            out = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.check(L.sq_align_pair_count(_ptr(partner), _ptr(cell_off), _ptr(d_off), _ptr(d_cols), nrec, int(Lcols), int(threshold),
+                                             _ptr(scratch), nbytes, _ptr(flat), _ptr(count), _ptr(first), cap, _ptr(out), _stream(dev)))
+            n, status = out.tolist()
+        if status:
+            raise RuntimeError("sq_align_pair_count: a pair table entry lies outside its record or the %d columns" % Lcols)
+        assert n <= cap
+        return flat[:n], count[:n], first[:n]
+
+    def window_pair_count(self, partner, cell_off, rec0, starts, lens, Ltot, cap=None):
+        """The pair table of sliding windows on the device (sq_window_pair_count): partner / cell_off = pair tables in
+        fold_tensors' layout, window k = record rec0 + k (its consensus row, in the window's own coordinates); starts int64
+        (non-decreasing, on the axis of Ltot positions on which the records follow one another) and lens int32: device
+        tensors.  Returns the device tensors (flat int64 = gi * Ltot + gj, count, cover, first int32) of the distinct
+        pairs, unordered.  `cap` (default 1 << 16) sizes the result buffers; the call is repeated with the true number when
+        it was too small (matrix_select's protocol).  Only that number comes to the host."""
+        import torch
+        L = _lib.load()
+        dev, nwin = partner.device, int(starts.numel())
+        assert starts.dtype == torch.int64 and lens.dtype == torch.int32 and int(lens.numel()) == nwin
+        assert partner.dtype == torch.int32 and cell_off.dtype == torch.int64 and int(cell_off.numel()) >= int(rec0) + nwin + 1
+        starts, lens = starts.contiguous(), lens.contiguous()
+        cap = 1 << 16 if cap is None else int(cap)
+
+        def call(res, cap, out):
+            _lib.check(L.sq_window_pair_count(_ptr(partner), _ptr(cell_off), int(rec0), nwin, _ptr(starts), _ptr(lens), int(Ltot),
+                                              _ptr(res[0]), _ptr(res[1]), _ptr(res[2]), _ptr(res[3]), cap, _ptr(out), _stream(dev)))
+
+        with torch.cuda.device(dev):
+            return _call_until_fits(dev, cap, (torch.int64, torch.int32, torch.int32, torch.int32), call,
+                                    "sq_window_pair_count: a pair table entry is not a pair inside its window, or a window "
+                                    "lies outside the %d positions or its table" % Ltot)
+
+    def score_tensors(self, recs, partner, row_start, row_rec):
+        """ScoreStruct, stems and metrics of given structures on the device (sq_score_structs_dev; SQRNdbnseq.py:958-970,
+        1249-1258).  recs: the records (score.ScoreRecord: prepared on the host once per record, however many rows it has);
+        partner: a flat int32 CUDA tensor of partner rows in input columns; row_start / row_rec: per row (host arrays) where
+        it starts in partner and its record.  Returns device tensors: scores float64[rows, 3], metrics float64[rows, 6],
+        status / npairs / nstems int32[rows], stems int32[S, 3], stem_off int64[rows + 1], ref_scores float64[records, 3],
+        ref_status int32[records].  No sq_batch.  Enqueued on the current stream; the one wait is for the number of stems,
+        which sizes their tensor."""
+        import torch
+        assert partner.is_cuda and partner.dtype == torch.int32 and partner.dim() == 1 and partner.is_contiguous()
+        L = _lib.load()
+        dev, R, rows = partner.device, len(recs), len(row_rec)
+        lens = np.array([rec.n for rec in recs], np.int64)
+        pos_off = np.zeros(R + 1, np.int64)
+        np.cumsum(lens, out=pos_off[1:])
+        cat = lambda parts, dt: np.concatenate([np.asarray(p, dt).reshape(-1) for p in parts] + [np.zeros(0, dt)])
+        has_reacts = np.array([rec.reacts is not None for rec in recs], np.uint8)
+        react_len = int(max((rec.n for rec in recs if rec.reacts is not None), default=0))
+        arrays = [pos_off, cat([rec.codes for rec in recs], np.uint8), has_reacts, np.array([rec.nsep for rec in recs], np.int32),
+                  cat([rec.known_partner for rec in recs], np.int32),
+                  np.array([len(rec.known) if rec.known is not None else -1 for rec in recs], np.int32),
+                  self._pow17_table(int(lens.max(initial=0))), np.asarray(row_start, np.int64).reshape(-1), np.asarray(row_rec, np.int32).reshape(-1)]
+        if react_len:
+            arrays.append(cat([np.asarray(rec.reacts, np.float64) if rec.reacts is not None else np.zeros(rec.n) for rec in recs], np.float64))
+        if rows:                                                     # (every row lies inside the tensor: the kernels trust it)
+            width = np.array([len(rec.seq) for rec in recs], np.int64)[arrays[8]]
+            assert int(arrays[7].min()) >= 0 and int((arrays[7] + width).max()) <= partner.numel(), "a row outside the partner tensor"
+        gaps = any(rec.has_gap for rec in recs)
+        if gaps:                                                     # (the maps between input columns and gap-free positions)
+            col_off = np.zeros(R + 1, np.int64)
+            np.cumsum([len(rec.colmap) for rec in recs], out=col_off[1:])
+            arrays += [col_off, cat([rec.colmap for rec in recs], np.int32), cat([rec.gfcol for rec in recs], np.int32)]
+        with torch.cuda.device(dev):
+            up = _upload_once([a if len(a) else np.zeros(1, a.dtype) for a in arrays], dev)
+            d = _lib.ScoreDesc(nrec=R, max_react_len=react_len, d_pos_off=_ptr(up[0]), d_codes=_ptr(up[1]), d_has_reacts=_ptr(up[2]),
+                               d_nsep=_ptr(up[3]), d_known=_ptr(up[4]), d_known_n=_ptr(up[5]), d_pow=_ptr(up[6]), pow_len=len(arrays[6]),
+                               d_reacts=_ptr(up[9]) if react_len else None)
+            if gaps:
+                d.d_col_off, d.d_colmap, d.d_gfcol = (_ptr(t) for t in up[-3:])
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            out = dict(scores=new((rows, 3), torch.float64), metrics=new((rows, 6), torch.float64), status=new(rows, torch.int32),
+                       npairs=new(rows, torch.int32), nstems=new(rows, torch.int32), ref_scores=new((R, 3), torch.float64),
+                       ref_status=new(R, torch.int32))
+            nbytes = int(L.sq_score_scratch(R))
+            scratch = new(nbytes // 4, torch.int32)
+            stem_off = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
+            o = _lib.ScoreRows(nrows=rows, d_partner=_ptr(partner), d_row_start=_ptr(up[7]), d_row_rec=_ptr(up[8]), d_status=_ptr(out["status"]),
+                               d_npairs=_ptr(out["npairs"]), d_nstems=_ptr(out["nstems"]), d_stem_off=_ptr(stem_off), d_stems=None, stem_cap=0,
+                               d_scores=_ptr(out["scores"]), d_metrics=_ptr(out["metrics"]), d_ref_scores=_ptr(out["ref_scores"]),
+                               d_ref_status=_ptr(out["ref_status"]))
+            stream = _stream(dev)
+            _lib.check(L.sq_score_structs_dev(C.byref(d), C.byref(o), 0, _ptr(scratch), nbytes, stream))
+            stem_off[1:] = torch.cumsum(out["nstems"], 0, dtype=torch.int64)
+            nstems = int(stem_off[-1].item())
+            out["stems"] = new((nstems, 3), torch.int32)
+            o.d_stems, o.stem_cap = (_ptr(out["stems"]) if nstems else None), nstems
+            _lib.check(L.sq_score_structs_dev(C.byref(d), C.byref(o), 1, _ptr(scratch), nbytes, stream))
+        out["stem_off"] = stem_off
+        return out
+
+    def _pow17_table(self, nmax):
+        """(k / 2) ** 1.7 for k <= 4 nmax with the host's pow, as ScoreStruct's `bpsum ** power` computes it (:884): a stem of
+        an n-nt record sums at most 4 x n / 2.  Kept for the longest record seen.  Python's float power IS the libm call the
+        reference makes; numpy's vectorised power may not be.  One pass of 4 n entries: ~20 ms once for a 32,768-nt record."""
+        have = self._pow17
+        if have is None or len(have) < 4 * nmax + 1:
+            have = self._pow17 = np.array([(0.5 * k) ** 1.7 for k in range(4 * max(nmax, 64) + 1)], np.float64)
+        return have[:4 * nmax + 1]

@@ -2,12 +2,15 @@
 drives libsquarna_hip.so through its C ABI.  PyTorch is plumbing here (device memory,
 stream, torch.distributed); all arithmetic runs in the hand-written gfx950 kernels.
 
+This module is batching and the fold / retry machinery (sub-batches, the capacity retry, alignment step 1 and entropy
+mode through Batch).  The batch-free device entries -- matrix_select, matrix_cells, first_fit, align_pair_count,
+window_pair_count, score_tensors -- live in device_calls.DeviceCalls, which HipEngine inherits.
+
 There is NO CPU fallback: without the built library or without a GPU the engine raises.
 Tests may install another engine with :func:`use_engine` (tests/ only use that to check
 the host-side text layer on CPU against the oracle).
 """
 import contextlib
-import ctypes as C
 import threading
 import weakref
 
@@ -18,6 +21,7 @@ from .dbn import gap_mask
 # every name callers outside this module take from `engine` (bench.py, tests/, tools/, api.py, align.py, core.py, parallel.py)
 from .records import Prepared, PackedRows  # noqa: F401
 from .batch import Batch, fold_concurrently
+from .device_calls import DeviceCalls, _upload_once
 from .results import unpack_result, packed_pair_tables, _Blocks, _BlockRun  # noqa: F401
 from .bpp import vienna_bpp, set_bpp_provider, bpp_terms, check_bpp_matrix  # noqa: F401
 from .plan import (pool_slots_wanted, pool_slots_wanted_many, pool_slot_cap, slot_bytes, default_structs,  # noqa: F401
@@ -114,20 +118,6 @@ class _TensorRun:
         self.tables, self.nstruct, self.lengths, self.source = tables, nstruct, lengths, source
 
 
-def _upload_once(arrays, device):
-    """The numpy arrays as torch tensors on `device`, through ONE host-to-device copy (every array starts 8-byte aligned)."""
-    import torch
-    offs, total = [], 0
-    for a in arrays:
-        offs.append(total)
-        total += (a.nbytes + 7) & ~7
-    host = np.zeros(max(total, 8), np.uint8)
-    for a, o in zip(arrays, offs):
-        host[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
-    dev = torch.from_numpy(host).to(device)
-    return [dev[o:o + a.nbytes].view(getattr(torch, a.dtype.name)).reshape(a.shape) for a, o in zip(arrays, offs)]
-
-
 def _tensor_results(batches):
     """fold_records(_tensors=True), fold_tensors' path: per batch [((its _TensorRun, record), None)].  The device tail's
     results leave as tensors formed on the device (Batch.result_tensors); a batch whose tail ran on the host is converted
@@ -172,7 +162,7 @@ def _tuple_results(batches):
     return [b.results_all() for b in batches]
 
 
-class HipEngine:
+class HipEngine(DeviceCalls):
     """Default engine: everything on the GPU through libsquarna_hip.so."""
     name = "hip"
     writes_blocks = True          # fold_records(..., _blocks=cfg): the library forms Predict's output blocks
@@ -196,8 +186,6 @@ class HipEngine:
         # max |M| of a shared stem matrix, remembered through a WEAK reference: the engine is process-wide and must not keep an
         # L x L device matrix (200 MB at L = 5000) alive after the alignment that owns it has ended
         self._sm_maxabs = (None, None)
-        #: score_tensors' table of (k / 2) ** 1.7, kept for the longest record seen (_pow17_table)
-        self._pow17 = None
 
     def fold_records(self, records, bpp=None, **opts):
         """records: list of (seq, reacts, restraints, dbn, paramsets, stemmatrix);
@@ -544,195 +532,6 @@ class HipEngine:
                 torch.cuda.synchronize(dev)
             lo = hi
         return matrix
-
-    def matrix_select(self, matrix, threshold, minspan=4):
-        """Device tensors (flat indices int64, values float64) of the upper cells >= threshold with span >= minspan of a
-        device matrix, unordered (sq_colmatrix_select); only the cells' number comes to the host."""
-        import torch
-        Lcols = int(matrix.shape[0])
-        cap = 1 << 16
-        stream = torch.cuda.current_stream(matrix.device)
-        while True:                                                # result buffers are torch tensors (caller-owned)
-            idx = torch.empty(cap, dtype=torch.int64, device=matrix.device)
-            val = torch.empty(cap, dtype=torch.float64, device=matrix.device)
-            cnt = torch.zeros(1, dtype=torch.int64, device=matrix.device)
-            _lib.check(_lib.load().sq_colmatrix_select(C.c_void_p(matrix.data_ptr()), Lcols, float(threshold), int(minspan),
-                                                       C.c_void_p(idx.data_ptr()), C.c_void_p(val.data_ptr()), cap,
-                                                       C.c_void_p(cnt.data_ptr()), C.c_void_p(stream.cuda_stream)))
-            n = int(cnt.item())
-            if n <= cap:
-                break
-            cap = n
-        return idx[:n], val[:n]
-
-    def matrix_cells(self, matrix, threshold, minspan=4, sort=True):
-        """(flat indices, values) of the upper cells >= threshold with span >= minspan of a device matrix,
-        sorted by flat index unless sort=False (MatrixToDBNs' candidates, SQRNdbnali.py:127-148)."""
-        idx, val = self.matrix_select(matrix, threshold, minspan)
-        idx, val = idx.cpu().numpy(), val.cpu().numpy()
-        if not sort:
-            return idx, val
-        order = np.argsort(idx, kind="stable")
-        return idx[order], val[order]
-
-    def first_fit(self, flat, Lcols, minspan=0):
-        """The greedy pass over ranked candidates on the device (sq_first_fit_dev): flat = int64 device tensor of cells
-        v * Lcols + w in rank order; a candidate of span >= minspan joins iff both of its columns are still free
-        (MatrixToDBNs' first structure SQRNdbnali.py:127-192 with minspan 4, Consensus :285-295 with none).  Returns
-        (partner int32[Lcols] on the device, -1 where free; info int32[4] on the device: status, rounds, pairs, live).
-        Enqueued on the current stream; nothing is waited for."""
-        import torch
-        flat = flat.contiguous()
-        assert flat.dtype == torch.int64 and flat.is_cuda and flat.dim() == 1
-        L = _lib.load()
-        n, dev = int(flat.numel()), flat.device
-        with torch.cuda.device(dev):
-            nbytes = int(L.sq_first_fit_scratch(n, int(Lcols)))
-            scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
-            partner = torch.empty(int(Lcols), dtype=torch.int32, device=dev)
-            info = torch.empty(4, dtype=torch.int32, device=dev)
-            _lib.check(L.sq_first_fit_dev(C.c_void_p(flat.data_ptr() if n else None), n, int(Lcols), int(minspan),
-                                          C.c_void_p(partner.data_ptr()), C.c_void_p(scratch.data_ptr()), nbytes,
-                                          C.c_void_p(info.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        return partner, info
-
-    def align_pair_count(self, partner, cell_off, gap_maps, Lcols, threshold=1):
-        """Consensus' dict on the device (sq_align_pair_count): partner / cell_off = the pair tables of fold_tensors (gap-free
-        coordinates), gap_maps = per record the int32 array of its positions' alignment columns.  Returns the device
-        tensors (flat int64 = v * Lcols + w, count int32, first int32) of the distinct column pairs that at least
-        `threshold` records' consensus rows hold, unordered; only their number comes to the host."""
-        import torch
-        L = _lib.load()
-        dev, nrec = partner.device, len(gap_maps)
-        col_off = np.zeros(nrec + 1, np.int32)
-        np.cumsum([len(g) for g in gap_maps], out=col_off[1:])
-        cols = np.concatenate(gap_maps).astype(np.int32) if nrec else np.zeros(0, np.int32)
-        assert int(cell_off.numel()) == nrec + 1
-        cap = max(int(col_off[-1]) // 2, 1)                          # (a record of n positions holds at most n / 2 pairs)
-        with torch.cuda.device(dev):
-            if not partner.numel():                                  # (every row all gaps: no table, no pair)
-                return tuple(torch.empty(0, dtype=dt, device=dev) for dt in (torch.int64, torch.int32, torch.int32))
-            d_off, d_cols = _upload_once([col_off, cols if len(cols) else np.zeros(1, np.int32)], dev)
-            nbytes = int(L.sq_align_pair_count_scratch(int(Lcols)))
-            scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
-            flat = torch.empty(cap, dtype=torch.int64, device=dev)
-            count = torch.empty(cap, dtype=torch.int32, device=dev)
-            first = torch.empty(cap, dtype=torch.int32, device=dev)
-            out = torch.empty(2, dtype=torch.int64, device=dev)
-            _lib.check(L.sq_align_pair_count(C.c_void_p(partner.data_ptr()), C.c_void_p(cell_off.data_ptr()),
-                                             C.c_void_p(d_off.data_ptr()), C.c_void_p(d_cols.data_ptr()), nrec, int(Lcols),
-                                             int(threshold), C.c_void_p(scratch.data_ptr()), nbytes, C.c_void_p(flat.data_ptr()),
-                                             C.c_void_p(count.data_ptr()), C.c_void_p(first.data_ptr()), cap,
-                                             C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-            n, status = out.tolist()
-        if status:
-            raise RuntimeError("sq_align_pair_count: a pair table entry lies outside its record or the %d columns" % Lcols)
-        assert n <= cap
-        return flat[:n], count[:n], first[:n]
-
-    def window_pair_count(self, partner, cell_off, rec0, starts, lens, Ltot, cap=None):
-        """The pair table of sliding windows on the device (sq_window_pair_count): partner / cell_off = pair tables in
-        fold_tensors' layout, window k = record rec0 + k (its consensus row, in the window's own coordinates); starts int64
-        (non-decreasing, on the axis of Ltot positions on which the records follow one another) and lens int32: device
-        tensors.  Returns the device tensors (flat int64 = gi * Ltot + gj, count, cover, first int32) of the distinct
-        pairs, unordered.  `cap` (default 1 << 16) sizes the result buffers; the call is repeated with the true number when
-        it was too small (matrix_select's protocol).  Only that number comes to the host."""
-        import torch
-        L = _lib.load()
-        dev, nwin = partner.device, int(starts.numel())
-        assert starts.dtype == torch.int64 and lens.dtype == torch.int32 and int(lens.numel()) == nwin
-        assert partner.dtype == torch.int32 and cell_off.dtype == torch.int64 and int(cell_off.numel()) >= int(rec0) + nwin + 1
-        starts, lens = starts.contiguous(), lens.contiguous()
-        cap = 1 << 16 if cap is None else int(cap)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
-            while True:
-                flat = torch.empty(cap, dtype=torch.int64, device=dev)
-                count, cover, first = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
-                out = torch.empty(2, dtype=torch.int64, device=dev)
-                _lib.check(L.sq_window_pair_count(C.c_void_p(partner.data_ptr()), C.c_void_p(cell_off.data_ptr()), int(rec0), nwin,
-                                                  C.c_void_p(starts.data_ptr()), C.c_void_p(lens.data_ptr()), int(Ltot),
-                                                  C.c_void_p(flat.data_ptr()), C.c_void_p(count.data_ptr()),
-                                                  C.c_void_p(cover.data_ptr()), C.c_void_p(first.data_ptr()), cap,
-                                                  C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)))
-                n, status = out.tolist()
-                if status:
-                    raise RuntimeError("sq_window_pair_count: a pair table entry is not a pair inside its window, or a window "
-                                       "lies outside the %d positions or its table" % Ltot)
-                if n <= cap:
-                    break
-                cap = n
-        return flat[:n], count[:n], cover[:n], first[:n]
-
-    def score_tensors(self, recs, partner, row_start, row_rec):
-        """ScoreStruct, stems and metrics of given structures on the device (sq_score_structs_dev; SQRNdbnseq.py:958-970,
-        1249-1258).  recs: the records (score.ScoreRecord: prepared on the host once per record, however many rows it has);
-        partner: a flat int32 CUDA tensor of partner rows in input columns; row_start / row_rec: per row (host arrays) where
-        it starts in partner and its record.  Returns device tensors: scores float64[rows, 3], metrics float64[rows, 6],
-        status / npairs / nstems int32[rows], stems int32[S, 3], stem_off int64[rows + 1], ref_scores float64[records, 3],
-        ref_status int32[records].  No sq_batch.  Enqueued on the current stream; the one wait is for the number of stems,
-        which sizes their tensor."""
-        import torch
-        assert partner.is_cuda and partner.dtype == torch.int32 and partner.dim() == 1 and partner.is_contiguous()
-        L = _lib.load()
-        dev, R, rows = partner.device, len(recs), len(row_rec)
-        lens = np.array([rec.n for rec in recs], np.int64)
-        pos_off = np.zeros(R + 1, np.int64)
-        np.cumsum(lens, out=pos_off[1:])
-        cat = lambda parts, dt: np.concatenate([np.asarray(p, dt).reshape(-1) for p in parts] + [np.zeros(0, dt)])
-        has_reacts = np.array([rec.reacts is not None for rec in recs], np.uint8)
-        react_len = int(max((rec.n for rec in recs if rec.reacts is not None), default=0))
-        arrays = [pos_off, cat([rec.codes for rec in recs], np.uint8), has_reacts, np.array([rec.nsep for rec in recs], np.int32),
-                  cat([rec.known_partner for rec in recs], np.int32),
-                  np.array([len(rec.known) if rec.known is not None else -1 for rec in recs], np.int32),
-                  self._pow17_table(int(lens.max(initial=0))), np.asarray(row_start, np.int64).reshape(-1), np.asarray(row_rec, np.int32).reshape(-1)]
-        if react_len:
-            arrays.append(cat([np.asarray(rec.reacts, np.float64) if rec.reacts is not None else np.zeros(rec.n) for rec in recs], np.float64))
-        if rows:                                                     # (every row lies inside the tensor: the kernels trust it)
-            width = np.array([len(rec.seq) for rec in recs], np.int64)[arrays[8]]
-            assert int(arrays[7].min()) >= 0 and int((arrays[7] + width).max()) <= partner.numel(), "a row outside the partner tensor"
-        gaps = any(rec.has_gap for rec in recs)
-        if gaps:                                                     # (the maps between input columns and gap-free positions)
-            col_off = np.zeros(R + 1, np.int64)
-            np.cumsum([len(rec.colmap) for rec in recs], out=col_off[1:])
-            arrays += [col_off, cat([rec.colmap for rec in recs], np.int32), cat([rec.gfcol for rec in recs], np.int32)]
-        with torch.cuda.device(dev):
-            up = _upload_once([a if len(a) else np.zeros(1, a.dtype) for a in arrays], dev)
-            ptr = lambda t: C.c_void_p(t.data_ptr())
-            d = _lib.ScoreDesc(nrec=R, max_react_len=react_len, d_pos_off=ptr(up[0]), d_codes=ptr(up[1]), d_has_reacts=ptr(up[2]),
-                               d_nsep=ptr(up[3]), d_known=ptr(up[4]), d_known_n=ptr(up[5]), d_pow=ptr(up[6]), pow_len=len(arrays[6]),
-                               d_reacts=ptr(up[9]) if react_len else None)
-            if gaps:
-                d.d_col_off, d.d_colmap, d.d_gfcol = (ptr(t) for t in up[-3:])
-            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-            out = dict(scores=new((rows, 3), torch.float64), metrics=new((rows, 6), torch.float64), status=new(rows, torch.int32),
-                       npairs=new(rows, torch.int32), nstems=new(rows, torch.int32), ref_scores=new((R, 3), torch.float64),
-                       ref_status=new(R, torch.int32))
-            nbytes = int(L.sq_score_scratch(R))
-            scratch = new(nbytes // 4, torch.int32)
-            stem_off = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
-            o = _lib.ScoreRows(nrows=rows, d_partner=ptr(partner), d_row_start=ptr(up[7]), d_row_rec=ptr(up[8]), d_status=ptr(out["status"]),
-                               d_npairs=ptr(out["npairs"]), d_nstems=ptr(out["nstems"]), d_stem_off=ptr(stem_off), d_stems=None, stem_cap=0,
-                               d_scores=ptr(out["scores"]), d_metrics=ptr(out["metrics"]), d_ref_scores=ptr(out["ref_scores"]),
-                               d_ref_status=ptr(out["ref_status"]))
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(L.sq_score_structs_dev(C.byref(d), C.byref(o), 0, ptr(scratch), nbytes, stream))
-            stem_off[1:] = torch.cumsum(out["nstems"], 0, dtype=torch.int64)
-            nstems = int(stem_off[-1].item())
-            out["stems"] = new((nstems, 3), torch.int32)
-            o.d_stems, o.stem_cap = (ptr(out["stems"]) if nstems else None), nstems
-            _lib.check(L.sq_score_structs_dev(C.byref(d), C.byref(o), 1, ptr(scratch), nbytes, stream))
-        out["stem_off"] = stem_off
-        return out
-
-    def _pow17_table(self, nmax):
-        """(k / 2) ** 1.7 for k <= 4 nmax with the host's pow, as ScoreStruct's `bpsum ** power` computes it (:884): a stem of
-        an n-nt record sums at most 4 x n / 2.  Kept for the longest record seen.  Python's float power IS the libm call the
-        reference makes; numpy's vectorised power may not be.  One pass of 4 n entries: ~20 ms once for a 32,768-nt record."""
-        have = self._pow17
-        if have is None or len(have) < 4 * nmax + 1:
-            have = self._pow17 = np.array([(0.5 * k) ** 1.7 for k in range(4 * max(nmax, 64) + 1)], np.float64)
-        return have[:4 * nmax + 1]
 
     def entropy_tensors(self, recs, interchainonly=False, M=1.8, B=-0.6, stem_matrix=None, bpp=None, scratch_bytes=None):
         """Entropy mode as data (SQRNdbnseq.py:520-545, 1087-1089; sq_entropy_rows): recs = [(seq, reacts, restraints,

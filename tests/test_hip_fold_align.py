@@ -258,3 +258,104 @@ def test_bad_arguments_are_refused_before_anything_is_enqueued():
     assert L.sq_align_pair_count(p, p, p, p, 1, 4, 1, p, 8, p, p, p, 4, p, None) == -1         # scratch too small
     torch.cuda.synchronize()
     assert buf.tolist() == [0] * 64
+
+
+# ---- the emission stage's flush inside the loop (sq_emit.h) ------------------------------------------------------------
+# The alignments above select far fewer than 768 cells per block; these inputs are dense enough that blocks flush their stage
+# inside the loop, carry a partly filled stage from one row into the next, and outgrow the first call's buffers.
+def _check_matrix_select(m, thr, minspan=4):
+    """HipEngine.matrix_select of the numpy matrix m against numpy's own selection; returns the expected mask."""
+    import torch
+    from squarna_amd.engine import HipEngine
+    L = m.shape[0]
+    v, w = np.indices((L, L))
+    mask = (w - v >= minspan) & (m >= thr)
+    exp = np.flatnonzero(mask.reshape(-1))
+    idx, val = HipEngine().matrix_select(torch.from_numpy(m).cuda(), thr, minspan)
+    assert idx.dtype == torch.int64 and val.dtype == torch.float64 and idx.is_cuda and val.is_cuda
+    idx, val = idx.cpu().numpy(), val.cpu().numpy()
+    assert len(idx) == len(val) == len(exp)
+    assert len(np.unique(idx)) == len(idx)                                   # no cell twice
+    assert np.array_equal(np.sort(idx), exp)
+    assert np.array_equal(val, m.reshape(-1)[idx])                           # bit for bit
+    assert (val == thr).any()                                                # (>=, not >)
+    return mask
+
+
+def test_matrix_select_partial_ballots_flush_inside_the_loop():
+    """L = 1100, one row per block, values 0..7: at threshold 4 about half of the upper cells pass (partial ballots in every
+    wave; row 0 stages ~550, so its block flushes once, at the end); at threshold 2 three quarters pass and the first rows
+    stage more than 768, so their blocks flush inside the loop as well."""
+    L = 1100
+    m = np.random.default_rng(1100).integers(0, 8, (L, L)).astype(np.float64)
+    half = _check_matrix_select(m, 4.0)
+    assert 0.45 < half.sum() / (np.arange(1, L - 3).sum()) < 0.55
+    dense = _check_matrix_select(m, 2.0)
+    assert dense[0].sum() > 768 and 0 < dense[0, -256:].sum() < 256
+
+
+def test_matrix_select_every_cell_two_rows_per_block_and_the_repeat():
+    """L = 2304, every cell at or above the threshold: 2,048 blocks, so blocks 0..255 take two rows and carry a partly
+    filled stage from one into the next; 2,646,150 cells, so the first call's 65,536 entries are too few and the call is
+    repeated with the true number."""
+    L = 2304
+    m = np.random.default_rng(2304).integers(4, 12, (L, L)).astype(np.float64)
+    mask = _check_matrix_select(m, 4.0)
+    assert mask.sum() == 2646150 > 1 << 16 and (L - 4) % 1024 and L > 2048
+
+
+def _antidiagonal_records(L, recs):
+    """Gap-free records of one table row each: record of `recs` entry r pairs i with (L - 1 - r) - i for i below its
+    partner.  Returns (partner, cell_off, gap_maps, flat cells per record)."""
+    partner = np.full((len(recs), L), -1, np.int32)
+    cells = []
+    for k, r in enumerate(recs):
+        s = L - 1 - r
+        i = np.arange((s + 1) // 2)
+        partner[k, i], partner[k, s - i] = s - i, i
+        cells.append(i.astype(np.int64) * L + (s - i))
+    return partner.reshape(-1), np.arange(len(recs) + 1, dtype=np.int64) * L, [np.arange(L, dtype=np.int32)] * len(recs), cells
+
+
+def _check_pair_count(L, recs, threshold):
+    """HipEngine.align_pair_count of such records against numpy's count; returns (flat, count, first) as expected."""
+    import torch
+    from squarna_amd.engine import HipEngine
+    partner, cell_off, gap_maps, cells = _antidiagonal_records(L, recs)
+    every = np.concatenate(cells)
+    owner = np.repeat(np.arange(len(recs)), [len(c) for c in cells])
+    flat, at, count = np.unique(every, return_index=True, return_counts=True)     # (at: the first occurrence, records in order)
+    keep = count >= threshold
+    exp = (flat[keep], count[keep], owner[at][keep])
+    rows = np.bincount(exp[0] // L, minlength=L)
+    got = HipEngine().align_pair_count(torch.from_numpy(partner).cuda(), torch.from_numpy(cell_off).cuda(), gap_maps, L, threshold)
+    assert [t.dtype for t in got] == [torch.int64, torch.int32, torch.int32] and all(t.is_cuda for t in got)
+    f, c, r = (t.cpu().numpy() for t in got)
+    order = np.argsort(f, kind="stable")
+    assert len(f) == len(exp[0]) and len(np.unique(f)) == len(f)
+    assert np.array_equal(f[order], exp[0]) and np.array_equal(c[order], exp[1]) and np.array_equal(r[order], exp[2])
+    return exp, rows
+
+
+def test_pair_count_dense_rows_flush_inside_the_loop():
+    """L = 2000, 900 records: 697,500 distinct column pairs, each held once; rows 0, 1 and 2 of the count table hold 900
+    cells each, so their blocks flush inside the loop."""
+    L = 2000
+    _, _, _, cells = _antidiagonal_records(L, range(900))
+    every = np.concatenate(cells)
+    assert len(np.unique(every)) == len(every) == 697500                       # no pair is held twice
+    assert (np.bincount(every // L)[:3] == 900).all() and 900 > 768            # rows beyond the in-loop bound
+    (flat, count, first), rows = _check_pair_count(L, list(range(900)), 1)
+    assert len(flat) == 697500 and (count == 1).all() and rows.max() == 900
+    assert np.array_equal(first, L - 1 - (flat // L + flat % L))               # (the record whose antidiagonal holds the cell)
+
+
+def test_pair_count_threshold_two_keeps_the_doubled_records():
+    """The same records with every even one given twice, threshold 2: only their pairs, count 2, first = the first copy."""
+    L = 2000
+    recs = [r for q in range(900) for r in ([q, q] if q % 2 == 0 else [q])]
+    first_copy = {r: recs.index(r) for r in range(0, 900, 2)}
+    (flat, count, first), _ = _check_pair_count(L, recs, 2)
+    assert len(flat) == sum((L - r) // 2 for r in range(0, 900, 2)) and (count == 2).all()
+    r = L - 1 - (flat // L + flat % L)
+    assert (r % 2 == 0).all() and np.array_equal(first, np.array([first_copy[int(x)] for x in r]))

@@ -483,6 +483,25 @@ SQ_API int sq_window_pair_count(const int32_t *d_partner, const int64_t *d_cell_
                                 const int32_t *d_len, int64_t Ltot, int64_t *d_flat, int32_t *d_count, int32_t *d_cover,
                                 int32_t *d_first, int64_t cap, uint64_t *d_out, void *hip_stream);
 
+/* ---- structure change of sequence variants (FoldMutants) -----------------------------------------------
+ * The pair tables d_partner / d_cell_off / d_lengths (sq_result_pairs_dev's layout; at least rec0 + nvar records) hold wild
+ * types among the first rec0 records and their substitution variants behind them: variant m is record rec0 + m, its wild
+ * type is record d_wt_rec[m] in [0, rec0), of the same length n, and both are read at row 0 (the consensus row).  The wild
+ * types lie on one axis of Ltot (<= 2^31 - 1) positions: record r's positions start at d_pos_off[r] (int64, at least rec0
+ * entries; only the entries d_wt_rec names are read).
+ * d_diff int32[nvar * 6], per variant: the wild type's pairs it lacks, its pairs the wild type lacks, the pairs of both, the
+ * positions whose partner differs, the lowest and the highest of them (-1, -1 without one).  d_pos_changed int32[Ltot]:
+ * per wild-type position the variants of its record whose partner there differs (cleared by the call, then added to).
+ * d_out[0] = 0, d_out[1] = 0, or 2 when a variant was invalid -- d_wt_rec outside [0, rec0), lengths that differ, a row
+ * longer than its table or outside the axis, a partner outside [-1, n), the position itself or one that does not point
+ * back --: that variant's six numbers and its additions to d_pos_changed are then unspecified, every other variant's are
+ * right, and no read leaves the two rows (csrc/sq_variants.h).
+ * One wave per variant.  Asynchronous on hip_stream, allocates nothing; 0, or -1 (bad argument: nothing enqueued; pointers
+ * that only variants need may be null when nvar = 0). */
+SQ_API int sq_variant_diff(const int32_t *d_partner, const int64_t *d_cell_off, const int64_t *d_lengths, int32_t rec0, int32_t nvar,
+                           const int32_t *d_wt_rec, const int64_t *d_pos_off, int64_t Ltot, int32_t *d_diff, int32_t *d_pos_changed,
+                           uint64_t *d_out, void *hip_stream);
+
 /* ---- measurement ------------------------------------------------------------
  * Kernel ids: 0 fill, 1 state, 2 stem_scan, 3 stem_score (+ select), 4 Edmonds, 5 Hungarian,
  * 6 Nussinov, 9 the bpp terms formed at sq_batch_create from bpp_matrix_dev (both kernels; recorded whether profiling

@@ -8,6 +8,9 @@ import numpy as np
 
 from . import _lib
 
+#: the most blocks sq_variant_diff launches, four variants each at a time (SQ_VARIANT_MAX_BLOCKS, csrc/sq_variants.h)
+VARIANT_DIFF_MAX_BLOCKS = 2048
+
 
 def _ptr(t):
     """The address of a device tensor as the C ABI takes it (None: a null pointer)."""
@@ -155,6 +158,31 @@ class DeviceCalls:
             return _call_until_fits(dev, cap, (torch.int64, torch.int32, torch.int32, torch.int32), call,
                                     "sq_window_pair_count: a pair table entry is not a pair inside its window, or a window "
                                     "lies outside the %d positions or its table" % Ltot)
+
+    def variant_diff(self, partner, cell_off, lengths, rec0, wt_rec, pos_off, Ltot):
+        """What substitution variants change against their wild types, on the device (sq_variant_diff): partner / cell_off /
+        lengths = pair tables in fold_tensors' layout, variant m = record rec0 + m, its wild type = record wt_rec[m] < rec0 of
+        the same length (both at their consensus rows); wt_rec int32 and pos_off int64 (where a record's positions start on
+        the axis of Ltot positions, at least rec0 entries): device tensors.  Returns the device tensors (diff int32[V, 6] =
+        lost, gained, kept, changed, first, last per variant; pos_changed int32[Ltot] = per wild-type position the variants
+        that changed its partner).  Only the two result words come to the host."""
+        import torch
+        dev, nvar = partner.device, int(wt_rec.numel())
+        assert partner.dtype == torch.int32 and cell_off.dtype == torch.int64 and lengths.dtype == torch.int64
+        assert wt_rec.dtype == torch.int32 and pos_off.dtype == torch.int64 and int(pos_off.numel()) >= int(rec0)
+        assert int(cell_off.numel()) >= int(rec0) + nvar + 1 and int(lengths.numel()) >= int(rec0) + nvar
+        lengths, wt_rec, pos_off = lengths.contiguous(), wt_rec.contiguous(), pos_off.contiguous()
+        with torch.cuda.device(dev):
+            diff = torch.empty((nvar, 6), dtype=torch.int32, device=dev)
+            pos_changed = torch.empty(int(Ltot), dtype=torch.int32, device=dev)
+            out = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.check(_lib.load().sq_variant_diff(_ptr(partner), _ptr(cell_off), _ptr(lengths), int(rec0), nvar, _ptr(wt_rec), _ptr(pos_off),
+                                                   int(Ltot), _ptr(diff), _ptr(pos_changed), _ptr(out), _stream(dev)))
+            status = out.tolist()[1]
+        if status:
+            raise RuntimeError("sq_variant_diff: a variant and its wild type differ in length or lie outside their tables or the %d "
+                               "positions, or a pair table entry is not a pair inside its row" % Ltot)
+        return diff, pos_changed
 
     def score_tensors(self, recs, partner, row_start, row_rec):
         """ScoreStruct, stems and metrics of given structures on the device (sq_score_structs_dev; SQRNdbnseq.py:958-970,

@@ -6,13 +6,6 @@
 
 #define SQ_ALGO_MAXN 4096          // longest sequence the device-side RunAlgo takes (LDS of the sizes / edges kernels)
 
-struct SqAlgoSize {                // per E / H / N job after its AnnotateStems pass (pinned, read by the host)
-    int32_t nedges;                // cells of its stems
-    int32_t nv;                    // distinct positions on them (Edmonds: graph vertices)
-    int32_t nok;                   // stems
-    int32_t raw_base;              // jobs whose edge weights need the host libm: where its nok stem scores start in the raw list
-                                   // (-1: weights from the paramset's table; -2: the list had no room)
-};
 // Edmonds / Hungarian jobs whose stem scores are not multiples of 2^-q (reactivity factors, non-dyadic weights): the sizes
 // kernel leaves the scores of their stems in pinned host memory, the host raises them to the power 1.7 with ITS libm -- what
 // CPython's `**` calls (SQRNalgos.py:101,122) -- in one loop over the array, and the edges kernel reads the weights there
@@ -22,19 +15,7 @@ struct SqAlgoRaw {
     uint32_t *ctr;                 // device: entries taken
     uint32_t cap;
 };
-struct SqAlgoJob {                 // per job, for the edges / finish kernels (pinned, written by the host once the sizes are known)
-    int32_t job, algo;             // batch job index, SQ_ALGO_*
-    SqMatchEdge *edges;            // device: the job's edge list
-    int32_t *vid2pos;              // device, Edmonds: graph vertex -> sequence position
-    const double *raw;             // pinned: stemscore ** 1.7 of the job's stems in survivor-list order (nullptr: the paramset's table)
-};
-struct SqAlgoStat {                // per launch of the finish kernel (device; sq_algo_publish_kernel copies it to the host)
-    uint32_t bad;                  // 1: blossom capacity exceeded, 2: stem capacity exceeded
-    uint32_t level_ovf;
-    unsigned long long max_pass_job;   // (scan passes << 32) | job row: the blossom kernel's critical path
-    unsigned long long passes, graphs;
-    long long max_events, max_n, max_m;
-};
+// (SqAlgoSize, SqAlgoJob, SqAlgoStat: sq_match.h -- the host plan of a chunk sizes them)
 
 #ifdef __HIPCC__
 extern "C" {

@@ -10,6 +10,7 @@
 #include <vector>
 #include "sq_host.h"
 #include "sq_match.h"
+#include "sq_algo_plan.h"
 
 #define HIPCK(x) do { int _r = sq_check((x), #x); if (_r) return _r; } while (0)
 
@@ -19,7 +20,7 @@ struct Pinned {                          // one pinned block from the process-wi
     ~Pinned() { sq_pinned_put(p); }
     int get(size_t bytes) { return sq_pinned_get((void **)&p, bytes); }
 };
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline size_t up256(size_t x) { return sq_up256(x); }
 
 // Graphs as the kernels want them: vertices renumbered in order of first appearance (networkx node order), a repeated
 // edge keeps its first position and takes the last weight (Graph.add_weighted_edges_from on an undirected Graph).
@@ -57,8 +58,9 @@ int build_graphs(int32_t ngraph, const int64_t *edge_off, const int32_t *eu, con
             G.edges.push_back(SqMatchEdge{a, b, ew ? ew[e] : 1.0});
         }
         J.n = (int32_t)lab.size(); J.nedges = (int32_t)(G.edges.size() - (size_t)J.edge_off);
-        J.scratch_off = (int64_t)G.scratch; G.scratch += up256(sq_mwm_scratch_bytes(J.n, J.nedges));
-        J.out_off = (int64_t)G.outints; G.outints += 2 * (size_t)J.n + 2;
+        const SqAlgoJobSize B = sq_algo_job_size(SQ_ALGO_E, J.n, (size_t)J.nedges);
+        J.scratch_off = (int64_t)G.scratch; G.scratch += B.need;
+        J.out_off = (int64_t)G.outints; G.outints += B.nout;
     }
     return 0;
 }
@@ -92,10 +94,9 @@ int build_cells(int32_t nprob, const int32_t *n, const int64_t *cell_off, const 
             C.edges.push_back(SqMatchEdge{a, b, val[e]});
         }
         J.nedges = (int32_t)(C.edges.size() - (size_t)J.edge_off);
-        J.scratch_off = (int64_t)C.scratch;
-        C.scratch += up256(nussinov ? sq_nussinov_scratch_bytes(J.n) : sq_lsap_scratch_bytes(J.n));
-        J.out_off = (int64_t)(nussinov ? C.outints / 2 : C.outints);
-        C.outints += nussinov ? 2 * ((size_t)J.n + 4) : (size_t)J.n;
+        const SqAlgoJobSize B = sq_algo_job_size(nussinov ? SQ_ALGO_N : SQ_ALGO_H, J.n, (size_t)J.nedges);
+        J.scratch_off = (int64_t)C.scratch; C.scratch += B.need;
+        J.out_off = (int64_t)(nussinov ? C.outints / 2 : C.outints); C.outints += B.nout;
     }
     return 0;
 }
@@ -129,7 +130,7 @@ int run_matching(int algo, const std::vector<SqMatchJob> &jobs, const std::vecto
     char *d_scr = (char *)d_codes + up256(ncodes + 16);
     if (codes && ncodes) HIPCK(hipMemcpyAsync(d_codes, codes, ncodes, hipMemcpyHostToDevice, st));
     const int rl = sq_launch_matching(algo, jobs.data(), (int)jobs.size(), p_jobs, p_edges, edges.size(), dev_edges, d_scr,
-                                      p_out, p_cnt, d_codes, nullptr, 0, st, p_jobs, (int32_t *)(pin.p + jb + eb + ob + cb), 1);
+                                      p_out, p_cnt, d_codes, nullptr, 0, st, p_jobs, (int32_t *)(pin.p + jb + eb + ob + cb), 1, sq_algo_knobs(0));
     if (rl) { hipStreamSynchronize(st); return sq_check((hipError_t)rl, "matching kernel launch"); }
     HIPCK(hipStreamSynchronize(st));                   // results are in host memory (the kernels wrote them in place)
     return read(p_out, p_cnt);
@@ -188,7 +189,7 @@ extern "C" int sq_lsap_workspace_bytes(int32_t nprob, const int32_t *n, const in
     size_t scratch = 0;
     for (int g = 0; g < nprob; g++) {
         if (n[g] < 0 || n[g] > 32000) { sq_set_error("matrix size out of range"); return -1; }
-        scratch += up256(sq_lsap_scratch_bytes(n[g]));
+        scratch += sq_algo_job_size(SQ_ALGO_H, n[g], 0).need;
     }
     *bytes = ws_bytes((size_t)std::max<int64_t>(cell_off[nprob], 0), 0, scratch);
     return 0;
@@ -214,7 +215,7 @@ extern "C" int sq_nussinov_workspace_bytes(int32_t nprob, const int32_t *n, cons
     size_t scratch = 0, ncodes = 0;
     for (int g = 0; g < nprob; g++) {
         if (n[g] < 0 || n[g] > 32000) { sq_set_error("matrix size out of range"); return -1; }
-        scratch += up256(sq_nussinov_scratch_bytes(n[g])); ncodes += (size_t)n[g];
+        scratch += sq_algo_job_size(SQ_ALGO_N, n[g], 0).need; ncodes += (size_t)n[g];
     }
     *bytes = ws_bytes((size_t)std::max<int64_t>(cell_off[nprob], 0), ncodes, scratch);
     return 0;

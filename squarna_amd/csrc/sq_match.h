@@ -37,16 +37,42 @@ SQ_HD static inline size_t sq_lsap_sparse_bytes(int n, int m)
     return (size_t)m * 8 + (size_t)n * nw * 4 + ((((size_t)n + 1) * 2 + 3) & ~(size_t)3) + (((size_t)n * nw * 2 + 3) & ~(size_t)3) + (size_t)m * 4 + 16;
 }
 SQ_HD static inline size_t sq_lsap_lds_bytes(int n, int m) { return sq_lsap_vec_bytes(n) + sq_lsap_sparse_bytes(n, m) + 64; }
-size_t sq_lsap_scratch_bytes(int n);
-size_t sq_nussinov_scratch_bytes(int n);
-size_t sq_mwm_scratch_bytes(int n, int nedges);
+// global scratch of one Hungarian / Nussinov job (Edmonds: sq_mwm_scratch_bytes, sq_algo_plan.h)
+static inline size_t sq_lsap_scratch_bytes(int n) { return ((size_t)n * n + 3 * (size_t)n) * 8 + 4 * (size_t)n * 4 + 2 * (size_t)n + 64; }
+static inline size_t sq_nussinov_scratch_bytes(int n)
+{
+    return 2 * (size_t)n * n * 8 + (size_t)n * n * 4 + (((size_t)n * n + 15) & ~(size_t)15) + 4 * (size_t)(n + 2) * 4 + 64;
+}
+
+// ---- records of the device-side RunAlgo (sq_algos_dev.hip) that the plan of a chunk (sq_algo_plan.h) sizes ----
+struct SqAlgoSize {                // per E / H / N job after its AnnotateStems pass (pinned, read by the host)
+    int32_t nedges;                // cells of its stems
+    int32_t nv;                    // distinct positions on them (Edmonds: graph vertices)
+    int32_t nok;                   // stems
+    int32_t raw_base;              // jobs whose edge weights need the host libm: where its nok stem scores start in the raw list
+                                   // (-1: weights from the paramset's table; -2: the list had no room)
+};
+struct SqAlgoJob {                 // per job, for the edges / finish kernels (pinned, written by the host once the sizes are known)
+    int32_t job, algo;             // batch job index, SQ_ALGO_*
+    SqMatchEdge *edges;            // device: the job's edge list
+    int32_t *vid2pos;              // device, Edmonds: graph vertex -> sequence position
+    const double *raw;             // pinned: stemscore ** 1.7 of the job's stems in survivor-list order (nullptr: the paramset's table)
+};
+struct SqAlgoStat {                // per launch of the finish kernel (device; sq_algo_publish_kernel copies it to the host)
+    uint32_t bad;                  // 1: blossom capacity exceeded, 2: stem capacity exceeded
+    uint32_t level_ovf;
+    unsigned long long max_pass_job;   // (scan passes << 32) | job row: the blossom kernel's critical path
+    unsigned long long passes, graphs;
+    long long max_events, max_n, max_m;
+};
 
 #ifdef __HIPCC__
+struct SqAlgoKnobs;                                      // sq_algo_plan.h
 void sq_max_dynamic_lds(const void *fn, int bytes);      // sq_host.hip: once per (kernel, device)
 int sq_launch_matching(int algo, const SqMatchJob *h_jobs, int nj, const SqMatchJob *jobs, const SqMatchEdge *edges,
                        size_t nedges, SqMatchEdge *dev_edges, char *d_scr, int32_t *out, int32_t *cnt,
                        const uint8_t *codes, uint32_t *job_flags, uint32_t flag_val, hipStream_t st,
-                       SqMatchJob *jobs_rw = nullptr, int32_t *bin_head = nullptr, int inflight = 1, bool dump = false);
+                       SqMatchJob *jobs_rw, int32_t *bin_head, int inflight, const SqAlgoKnobs &kn, bool dump = false);
 extern "C" {
 __global__ void sq_lsap_kernel(const SqMatchJob *jobs, const SqMatchEdge *edges, char *scratch, int32_t *col4row_out,
                                int lds_bytes);

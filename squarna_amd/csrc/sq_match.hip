@@ -23,6 +23,7 @@
 #include <vector>
 #include <algorithm>
 #include "sq_blossom.h"
+#include "sq_algo_plan.h"
 
 // ------------------------------------------------------------------------------------
 // LSAP: one wave per job.  Layout of the job's scratch (doubles then ints), nc = n:
@@ -479,88 +480,26 @@ extern "C" __global__ void sq_flag_kernel(uint32_t *flag, uint32_t value)
     *flag = value;
 }
 
+// the switches the plan of a chunk honours (sq_algo_plan.h reads no environment itself)
+SqAlgoKnobs sq_algo_knobs(int lsap_classes)
+{
+    const SqTuning &tu = sq_tuning();
+    SqAlgoKnobs kn;
+    kn.mwm_classes = tu.mwm_classes; kn.lsap_classes = lsap_classes;
+    kn.mwm_bin_waves = tu.mwm_bin_waves; kn.mwm_bin_bytes = tu.mwm_bin_bytes; kn.mwm_all_cap = tu.mwm_all_cap;
+    kn.mwm_nolds = tu.mwm_nolds; kn.nuss_threads = tu.nuss_threads;
+    return kn;
+}
+
 // Launch configuration of the three matching kernels (dynamic LDS sized for the largest job of the launch), shared
 // by the fold path (sq_algos.hip) and the graph-level C entries (sq_graph.hip).  jobs / edges: what the kernels read
 // (pinned host or device memory); h_jobs: the same table on the host; dev_edges: device room for the edge list, used
 // only when some blossom job has to run in global memory.  Asynchronous on st.
-// Packs the blossom graphs of one launch into bins (blocks) by LDS need, first fit in decreasing order.
-//   * a graph gets its whole state + edge list in LDS when that is at most `all_cap`, else only the hot part (the rest in
-//     its global scratch), else just the algorithm object (global-memory run);
-//   * a bin holds at most `waves` graphs and `cap` bytes; with one batch in flight every graph has its own block (spread
-//     over the CUs: latency), with several the bins fill up so that all batches' graphs are resident together and the
-//     scoring kernels still find LDS (throughput): waves = ceil(graphs x inflight / 256), cap 150 KB -> 96 KB, all_cap
-//     150 KB -> 48 KB from three batches in flight on.  SQ_MWM_BIN_WAVES / SQ_MWM_BIN_BYTES / SQ_MWM_ALL_CAP override.
-// Writes lds_off / lds_bytes / next of jobs_rw (the table the kernel reads) and bin_head[0..nbins).
-void sq_mwm_plan(const SqMatchJob *h_jobs, SqMatchJob *jobs_rw, int nj, int32_t *bin_head, int inflight, int &nbins, int &waves,
-                 size_t &lds, bool &all_in_lds, bool dump)
-{
-    const SqTuning &tu = sq_tuning();
-    const int env_waves = tu.mwm_bin_waves;
-    const long env_cap = tu.mwm_bin_bytes, env_all = tu.mwm_all_cap;
-    const bool nolds = tu.mwm_nolds;
-    const size_t hdr = (sizeof(SqBlossom) + 15) & ~(size_t)15;
-    const bool many = inflight >= 3;
-    // A launch (or the launches in flight together) with more graphs than the chip has room for at one graph per CU is a
-    // throughput problem: every graph keeps only the hot part of its state in LDS (~4 KB; the rest in its global scratch,
-    // +14 % time per graph) and a block holds four of them in 40 KB, so that ALL graphs are resident at once -- the kernel
-    // then lasts as long as its slowest graph -- and the scoring kernels of the greedy rounds still find LDS on every CU.
-    // Measured on 24 SRtest150 sets in one batch (4,296 graphs): 11.5 ms with 150 KB bins, 6.6 ms this way.
-    // ... and so is a launch of hundreds of LARGE graphs (hot part beyond a crowd's 40 KB bin: 500 vertices and 17,000 edges take
-    // 50 KB) beside the rounds of the same batch's pools: 822 such graphs fill the LDS of every CU for 75 ms, during which the
-    // round kernel does not run (round 6: 1,000 records of 500 nt under pools of a thousand 313 -> 278 ms with the graphs' state
-    // in global memory; at 700 records the same either way, at 500 and fewer the longer Edmonds kernel is what the fold waits for)
-    size_t hot_max = 0;
-    for (int q = 0; q < nj; q++) hot_max = std::max(hot_max, SqBlossom::hot_bytes(h_jobs[q].n, h_jobs[q].nedges, 2));
-    const bool crowd = (long long)nj * std::max(1, inflight) >= 1024 || (nj >= 768 && hot_max + 16 + ((sizeof(SqBlossom) + 15) & ~(size_t)15) > 40 * 1024);
-    size_t cap = env_cap > 0 ? (size_t)env_cap : (crowd ? 40 * 1024 : many ? 96 * 1024 : 150 * 1024);
-    cap = std::min<size_t>(cap, 150 * 1024);
-    const size_t all_cap = env_all > 0 ? (size_t)env_all : (crowd ? 1 : many ? 48 * 1024 : 150 * 1024);
-    waves = env_waves > 0 ? env_waves : (crowd ? 4 : (int)(((long long)nj * std::max(1, inflight) + 255) / 256));
-    waves = std::max(1, std::min(waves, 8));
-    std::vector<size_t> need(nj);
-    all_in_lds = true;
-    for (int q = 0; q < nj; q++) {
-        const int n = h_jobs[q].n, m = h_jobs[q].nedges;
-        const size_t full = SqBlossom::scratch_bytes(n, m, 1) + (((size_t)m * sizeof(SqMatchEdge) + 15) & ~(size_t)15) + 16;
-        const size_t hot = SqBlossom::hot_bytes(n, m, 2) + 16;
-        size_t take = hdr;
-        if (n > 0 && !nolds) {
-            if (hdr + full <= std::min(all_cap, cap)) take = hdr + full;
-            else if (hdr + hot <= cap) take = hdr + hot;
-        }
-        if (n > 0 && take != hdr + full) all_in_lds = false;
-        need[q] = (take + 15) & ~(size_t)15;
-    }
-    std::vector<int> ord(nj);
-    for (int q = 0; q < nj; q++) ord[q] = q;
-    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return need[x] > need[y]; });
-    std::vector<size_t> used; std::vector<int> cnt, tail;
-    nbins = 0; lds = 0;
-    size_t first_open = 0;                               // bins before it are full (by count)
-    for (int r = 0; r < nj; r++) {
-        const int q = ord[r];
-        size_t k = first_open;
-        while (k < used.size() && (cnt[k] >= waves || used[k] + need[q] > cap)) k++;
-        if (k == used.size()) { used.push_back(0); cnt.push_back(0); tail.push_back(-1); bin_head[k] = q; nbins++; }
-        else jobs_rw[tail[k]].next = q;
-        jobs_rw[q].lds_off = (int32_t)used[k]; jobs_rw[q].lds_bytes = (int32_t)need[q]; jobs_rw[q].next = -1;
-        used[k] += need[q]; cnt[k]++; tail[k] = q;
-        lds = std::max(lds, used[k]);
-        while (first_open < used.size() && cnt[first_open] >= waves) first_open++;
-    }
-    lds = (lds + 255) & ~(size_t)255;
-    if (dump) {
-        size_t tot = 0; int nfull = 0;
-        for (int q = 0; q < nj; q++) { tot += need[q]; nfull += need[q] > hdr + SqBlossom::hot_bytes(h_jobs[q].n, h_jobs[q].nedges, 2) + 32; }
-        fprintf(stderr, "[mwm plan] %d graphs (inflight %d): %d bins of <= %d waves, %zu B of LDS per block, %zu B needed in all, %d graphs fully in LDS\n",
-                nj, inflight, nbins, waves, lds, tot, nfull);
-    }
-}
-
+// The blossom graphs of one launch are packed into bins (blocks) by LDS need: sq_mwm_plan (sq_algo_plan.h).
 int sq_launch_matching(int algo, const SqMatchJob *h_jobs, int nj, const SqMatchJob *jobs, const SqMatchEdge *edges,
                        size_t nedges, SqMatchEdge *dev_edges, char *d_scr, int32_t *out, int32_t *cnt,
                        const uint8_t *codes, uint32_t *job_flags, uint32_t flag_val, hipStream_t st,
-                       SqMatchJob *jobs_rw, int32_t *bin_head, int inflight, bool dump)
+                       SqMatchJob *jobs_rw, int32_t *bin_head, int inflight, const SqAlgoKnobs &kn, bool dump)
 {
     int maxn = 0, maxm = 0;
     for (int q = 0; q < nj; q++) { maxn = maxn > h_jobs[q].n ? maxn : h_jobs[q].n; maxm = maxm > h_jobs[q].nedges ? maxm : h_jobs[q].nedges; }
@@ -573,49 +512,26 @@ int sq_launch_matching(int algo, const SqMatchJob *h_jobs, int nj, const SqMatch
         if (lds > 150 * 1024) lds = sq_lsap_vec_bytes(maxn) + 64 < 150 * 1024 ? sq_lsap_vec_bytes(maxn) + 64 : 150 * 1024;   // vectors only
         hipLaunchKernelGGL(sq_lsap_kernel, dim3(nj), dim3(64), lds, st, jobs, edges, d_scr, out, (int)lds);
     } else if (algo == 2) {                              // SQ_ALGO_N
-        // an anti-diagonal of the DP has at most n cells: no more waves than that keeps busy (the block holds its wave slots
-        // through the single-threaded BackTrack too)
-        // (with the chip crowded ONE wave per job: a block of three waves holds three wave slots through every barrier-separated
-        // diagonal, and wave slots are what a crowded chip runs out of -- a lane then takes up to three cells of a diagonal)
-        const int env_thr = sq_tuning().nuss_threads;
-        // ... and so is a launch of hundreds of LARGE graphs (hot part beyond a crowd's 40 KB bin: 500 vertices and 17,000 edges take
-    // 50 KB) beside the rounds of the same batch's pools: 822 such graphs fill the LDS of every CU for 75 ms, during which the
-    // round kernel does not run (round 6: 1,000 records of 500 nt under pools of a thousand 313 -> 278 ms with the graphs' state
-    // in global memory; at 700 records the same either way, at 500 and fewer the longer Edmonds kernel is what the fold waits for)
-    size_t hot_max = 0;
-    for (int q = 0; q < nj; q++) hot_max = std::max(hot_max, SqBlossom::hot_bytes(h_jobs[q].n, h_jobs[q].nedges, 2));
-    const bool crowd = (long long)nj * std::max(1, inflight) >= 1024 || (nj >= 768 && hot_max + 16 + ((sizeof(SqBlossom) + 15) & ~(size_t)15) > 40 * 1024);
-        const int nthr = env_thr ? env_thr : crowd ? 64 : std::max(64, std::min(256, (maxn + 63) / 64 * 64));
+        const int nthr = sq_nussinov_threads(h_jobs, nj, maxn, inflight, kn);
         hipLaunchKernelGGL(sq_nussinov_kernel, dim3(nj), dim3(nthr), 0, st, jobs, edges, codes, d_scr, out, cnt, jobs_rw ? 1 : 0);
     } else {                                             // SQ_ALGO_E
         // bins: see sq_mwm_plan.  The plan writes each job's LDS slice into the job table the kernel reads.
-        int nbins = 0, waves = 1; size_t lds = 0; bool all_in_lds = true;
-        sq_mwm_plan(h_jobs, jobs_rw, nj, bin_head, inflight, nbins, waves, lds, all_in_lds, dump);
+        const SqMwmPlan P = sq_mwm_plan(h_jobs, jobs_rw, nj, bin_head, inflight, kn, dump);
+        const size_t lds = P.lds;
         sq_max_dynamic_lds((const void *)sq_mwm_kernel, 156 * 1024);
-        if (!all_in_lds && dev_edges != edges) {
+        if (!P.all_in_lds && dev_edges != edges) {
             // some job keeps its adjacency in global memory and walks the edges in place: give the launch a device copy
             hipError_t e = hipMemcpyAsync(dev_edges, edges, nedges * sizeof(SqMatchEdge), hipMemcpyHostToDevice, st);
             if (e != hipSuccess) return (int)e;
             edges = dev_edges;
         }
-        if (waves == 1) {
+        if (P.waves == 1) {
             // one graph per block: blocks in table order, every block with the LDS of the launch's largest graph
             sq_max_dynamic_lds((const void *)sq_mwm_single_kernel, 156 * 1024);
-            const size_t hdr = (sizeof(SqBlossom) + 15) & ~(size_t)15;
-            const size_t one = lds > hdr ? lds - hdr : 0;
+            const size_t one = lds > sq_blossom_hdr() ? lds - sq_blossom_hdr() : 0;
             hipLaunchKernelGGL(sq_mwm_single_kernel, dim3(nj), dim3(64), one, st, jobs, edges, d_scr, out, (int)one, job_flags, flag_val);
         } else
-            hipLaunchKernelGGL(sq_mwm_kernel, dim3(nbins), dim3(64 * waves), lds, st, jobs, bin_head, edges, d_scr, out, job_flags, flag_val);
+            hipLaunchKernelGGL(sq_mwm_kernel, dim3(P.nbins), dim3(64 * P.waves), lds, st, jobs, bin_head, edges, d_scr, out, job_flags, flag_val);
     }
     return (int)hipGetLastError();
 }
-
-size_t sq_lsap_scratch_bytes(int n)
-{
-    return ((size_t)n * n + 3 * (size_t)n) * 8 + 4 * (size_t)n * 4 + 2 * (size_t)n + 64;
-}
-size_t sq_nussinov_scratch_bytes(int n)
-{
-    return 2 * (size_t)n * n * 8 + (size_t)n * n * 4 + (((size_t)n * n + 15) & ~(size_t)15) + 4 * (size_t)(n + 2) * 4 + 64;
-}
-size_t sq_mwm_scratch_bytes(int n, int nedges) { return SqBlossom::scratch_bytes(n, nedges); }

@@ -502,6 +502,30 @@ SQ_API int sq_variant_diff(const int32_t *d_partner, const int64_t *d_cell_off, 
                            const int32_t *d_wt_rec, const int64_t *d_pos_off, int64_t Ltot, int32_t *d_diff, int32_t *d_pos_changed,
                            uint64_t *d_out, void *hip_stream);
 
+/* ---- what two chains do to one another (FoldDuplex) --------------------------------------------------------
+ * Two sets of pair tables in sq_result_pairs_dev's layout, which may be one allocation: nsolo records folded alone
+ * (d_partner_s / d_cell_off_s / d_lengths_s) and ndup duplex records (d_partner_d / d_cell_off_d / d_lengths_d).  Duplex k is
+ * the chain of solo record d_a_rec[k] (nA positions), one separator column and the chain of solo record d_b_rec[k] (nB
+ * positions), both int32 in [0, nsolo) and possibly the same record: its row has nA + 1 + nB entries, entry nA the
+ * separator.  All rows are read at row 0 (the consensus row).  The solo records lie on one axis of Ltot (<= 2^31 - 1)
+ * positions: record r's positions start at d_pos_off[r] (int64[nsolo + 1]).
+ * d_summary int32[ndup * 9], per duplex, pairs counted at their 5' ends: the pairs between the chains, the pairs inside
+ * chain A, inside chain B, the pairs of A alone whose 5' end has another partner or none in the duplex, the same for B (a
+ * partner q of B alone corresponds to q + nA + 1), the lowest and the highest position of A with a partner in B, the same
+ * for B in B's own coordinates (-1, -1 without one).  d_bound int32[Ltot]: per solo position the duplexes in which it
+ * pairs across the separator, in either role (cleared by the call, then added to).
+ * d_out[0] = 0, d_out[1] = 0, or 2 when a duplex was invalid -- a chain outside [0, nsolo), a duplex row that is not
+ * nA + 1 + nB entries long, a row longer than its table or outside the axis, a paired separator column, a partner outside
+ * [-1, its row's length), the position itself or one that does not point back --: that duplex's nine numbers and its
+ * additions to d_bound are then unspecified, every other duplex's are right, and no read leaves the three rows
+ * (csrc/sq_duplex.h).
+ * One wave per duplex.  Asynchronous on hip_stream, allocates nothing; 0, or -1 (bad argument: nothing enqueued; pointers
+ * that only duplexes need may be null when ndup = 0, which clears d_out and d_bound). */
+SQ_API int sq_duplex_summary(const int32_t *d_partner_s, const int64_t *d_cell_off_s, const int64_t *d_lengths_s, int32_t nsolo,
+                             const int32_t *d_partner_d, const int64_t *d_cell_off_d, const int64_t *d_lengths_d, int32_t ndup,
+                             const int32_t *d_a_rec, const int32_t *d_b_rec, const int64_t *d_pos_off, int64_t Ltot,
+                             int32_t *d_summary, int32_t *d_bound, uint64_t *d_out, void *hip_stream);
+
 /* ---- measurement ------------------------------------------------------------
  * Kernel ids: 0 fill, 1 state, 2 stem_scan, 3 stem_score (+ select), 4 Edmonds, 5 Hungarian,
  * 6 Nussinov, 9 the bpp terms formed at sq_batch_create from bpp_matrix_dev (both kernels; recorded whether profiling

@@ -10,6 +10,8 @@ from . import _lib
 
 #: the most blocks sq_variant_diff launches, four variants each at a time (SQ_VARIANT_MAX_BLOCKS, csrc/sq_variants.h)
 VARIANT_DIFF_MAX_BLOCKS = 2048
+#: the most blocks sq_duplex_summary launches, four duplexes each at a time (SQ_DUPLEX_MAX_BLOCKS, csrc/sq_duplex.h)
+DUPLEX_SUMMARY_MAX_BLOCKS = 2048
 
 
 def _ptr(t):
@@ -183,6 +185,40 @@ class DeviceCalls:
             raise RuntimeError("sq_variant_diff: a variant and its wild type differ in length or lie outside their tables or the %d "
                                "positions, or a pair table entry is not a pair inside its row" % Ltot)
         return diff, pos_changed
+
+    def duplex_summary(self, partner_s, cell_off_s, lengths_s, partner_d, cell_off_d, lengths_d, a_rec, b_rec, pos_off, Ltot):
+        """What two chains do to one another, on the device (sq_duplex_summary): partner_s / cell_off_s / lengths_s = the pair
+        tables of the records folded alone, partner_d / cell_off_d / lengths_d = those of the duplex records, both in
+        fold_tensors' layout and possibly views of one allocation; duplex k = the chain of solo record a_rec[k], a separator
+        column and the chain of solo record b_rec[k] (all three at their consensus rows); a_rec / b_rec int32 and pos_off
+        int64 (where a solo record's positions start on the axis of Ltot positions, one entry more than there are solo
+        records): device tensors.  The duplex tables may be None when there is no duplex.  Returns the device tensors
+        (summary int32[P, 9] = inter, intra_a, intra_b, lost_a, lost_b, a_first, a_last, b_first, b_last per duplex; bound
+        int32[Ltot] = per solo position the duplexes in which it pairs across the separator).  Only the two result words come
+        to the host."""
+        import torch
+        dev, nsolo, ndup = partner_s.device, int(lengths_s.numel()), int(a_rec.numel())
+        assert partner_s.dtype == torch.int32 and cell_off_s.dtype == torch.int64 and lengths_s.dtype == torch.int64
+        assert a_rec.dtype == torch.int32 and b_rec.dtype == torch.int32 and int(b_rec.numel()) == ndup
+        assert pos_off.dtype == torch.int64 and int(pos_off.numel()) >= nsolo + 1 and int(cell_off_s.numel()) >= nsolo + 1
+        if ndup:
+            assert partner_d.dtype == torch.int32 and cell_off_d.dtype == torch.int64 and lengths_d.dtype == torch.int64
+            assert int(cell_off_d.numel()) >= ndup + 1 and int(lengths_d.numel()) >= ndup
+            cell_off_d, lengths_d = cell_off_d.contiguous(), lengths_d.contiguous()
+        cell_off_s, lengths_s, a_rec, b_rec, pos_off = (t.contiguous() for t in (cell_off_s, lengths_s, a_rec, b_rec, pos_off))
+        with torch.cuda.device(dev):
+            summary = torch.empty((ndup, 9), dtype=torch.int32, device=dev)
+            bound = torch.empty(int(Ltot), dtype=torch.int32, device=dev)
+            out = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.check(_lib.load().sq_duplex_summary(_ptr(partner_s), _ptr(cell_off_s), _ptr(lengths_s), nsolo,
+                                                     _ptr(partner_d if ndup else None), _ptr(cell_off_d if ndup else None),
+                                                     _ptr(lengths_d if ndup else None), ndup, _ptr(a_rec), _ptr(b_rec), _ptr(pos_off),
+                                                     int(Ltot), _ptr(summary), _ptr(bound), _ptr(out), _stream(dev)))
+            status = out.tolist()[1]
+        if status:
+            raise RuntimeError("sq_duplex_summary: a duplex does not consist of its two chains and a separator column, a row lies "
+                               "outside its table or the %d positions, or a pair table entry is not a pair inside its row" % Ltot)
+        return summary, bound
 
     def score_tensors(self, recs, partner, row_start, row_rec):
         """ScoreStruct, stems and metrics of given structures on the device (sq_score_structs_dev; SQRNdbnseq.py:958-970,

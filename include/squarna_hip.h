@@ -526,6 +526,30 @@ SQ_API int sq_duplex_summary(const int32_t *d_partner_s, const int64_t *d_cell_o
                              const int32_t *d_a_rec, const int32_t *d_b_rec, const int64_t *d_pos_off, int64_t Ltot,
                              int32_t *d_summary, int32_t *d_bound, uint64_t *d_out, void *hip_stream);
 
+/* ---- covariation evidence for alignment columns (Covariation) ----------------------------------------------
+ * d_rows uint8[R * L]: the ASCII rows of an alignment of R rows and L columns, row after row.  A byte is upper-cased and T
+ * reads as U; it is then A, C, G, U, a gap ('-', '.', '~') or "other".  For columns v < w, over the rows: c[t] = the rows
+ * whose two letters are the pair type t of AU UA GC CG GU UG (in this order), both_gap = the rows with a gap in both columns,
+ * and cov = the sum over t < t' of c[t] * c[t'] * d(t, t') with d the Hamming distance of the two two-letter strings -- the
+ * sum, over the unordered pairs of rows that both hold a canonical pair, of the distance of their pairs.  A record is the
+ * seven int32 counts (c[0..5], both_gap) and cov (int64); bp_rows = the sum of c, incompatible = R - bp_rows - both_gap.
+ * Both entries first write the rows as five bit planes of 64 rows per word into d_scratch (sq_covariation_scratch(R, L)
+ * bytes, 8-byte aligned; csrc/sq_covar.h has the layout).
+ * sq_covariation_scan: every cell with w - v >= minspan, as an all-pairs scan in tiles of columns from LDS; a cell with
+ * bp_rows >= min_rows and cov >= min_cov leaves one record, unordered: d_flat = v * L + w, d_counts[7], d_cov.
+ * d_out[0] = the number of such cells (may exceed cap: then only cap were stored and nothing is written beyond cap),
+ * d_out[1] = 0.
+ * sq_covariation_pairs: the records of the P column pairs d_pairs int32[P * 2] = (v, w), in their order.  d_out[0] = 0,
+ * d_out[1] = 0, or 2 when a pair was not 0 <= v < w < L: that pair's record is all zero, every other record is right.
+ * Asynchronous on hip_stream, allocate nothing; 0, or -1 (a null pointer, R < 1, L < 1, scratch too small, a negative
+ * minspan, threshold, cap or P: nothing enqueued; the record pointers may be null when cap or P is 0). */
+SQ_API size_t sq_covariation_scratch(int32_t R, int32_t L);
+SQ_API int sq_covariation_scan(const uint8_t *d_rows, int32_t R, int32_t L, int32_t minspan, int32_t min_rows, int64_t min_cov,
+                               void *d_scratch, size_t scratch_bytes, int64_t *d_flat, int32_t *d_counts, int64_t *d_cov, int64_t cap,
+                               uint64_t *d_out, void *hip_stream);
+SQ_API int sq_covariation_pairs(const uint8_t *d_rows, int32_t R, int32_t L, const int32_t *d_pairs, int64_t P, void *d_scratch,
+                                size_t scratch_bytes, int32_t *d_counts, int64_t *d_cov, uint64_t *d_out, void *hip_stream);
+
 /* ---- measurement ------------------------------------------------------------
  * Kernel ids: 0 fill, 1 state, 2 stem_scan, 3 stem_score (+ select), 4 Edmonds, 5 Hungarian,
  * 6 Nussinov, 9 the bpp terms formed at sq_batch_create from bpp_matrix_dev (both kernels; recorded whether profiling

@@ -12,6 +12,11 @@ from . import _lib
 VARIANT_DIFF_MAX_BLOCKS = 2048
 #: the most blocks sq_duplex_summary launches, four duplexes each at a time (SQ_DUPLEX_MAX_BLOCKS, csrc/sq_duplex.h)
 DUPLEX_SUMMARY_MAX_BLOCKS = 2048
+#: sq_covariation_scan's tile of columns, the 64-row words it keeps in LDS at a time and the most blocks it launches
+#: (SQ_COV_TILE, SQ_COV_WORD_CHUNK, SQ_COV_MAX_BLOCKS, csrc/sq_covar.h)
+COVAR_TILE = 32
+COVAR_WORD_CHUNK = 4
+COVAR_MAX_BLOCKS = 2048
 
 
 def _ptr(t):
@@ -41,14 +46,16 @@ def _upload_once(arrays, device):
 
 def _call_until_fits(device, cap, dtypes, call, status_error):
     """The protocol of the entries that emit a number of records nobody knows beforehand (sq_colmatrix_select,
-    sq_window_pair_count): result tensors of `cap` entries, one per dtype, are allocated on `device`; call(tensors, cap, out)
+    sq_window_pair_count): result tensors of `cap` entries, one per dtype (a pair (dtype, n): `cap` rows of n), are allocated
+    on `device`; call(tensors, cap, out)
     enqueues the entry, which leaves (records, status) in the two int64 words of `out` -- it counts every record, also those
     beyond cap; the two words are read once.  RuntimeError(status_error) on a status; the call is repeated once, with cap =
     the true number, when that was larger.  Returns the tensors cut to the records' number: only that number comes to the
     host."""
     import torch
     while True:                                                    # result buffers are torch tensors (caller-owned)
-        tensors = [torch.empty(cap, dtype=dt, device=device) for dt in dtypes]
+        tensors = [torch.empty((cap, dt[1]), dtype=dt[0], device=device) if isinstance(dt, tuple) else torch.empty(cap, dtype=dt, device=device)
+                   for dt in dtypes]
         out = torch.zeros(2, dtype=torch.int64, device=device)
         call(tensors, cap, out)
         n, status = out.tolist()
@@ -219,6 +226,51 @@ class DeviceCalls:
             raise RuntimeError("sq_duplex_summary: a duplex does not consist of its two chains and a separator column, a row lies "
                                "outside its table or the %d positions, or a pair table entry is not a pair inside its row" % Ltot)
         return summary, bound
+
+    def covariation_scan(self, rows, minspan=4, min_rows=1, min_cov=1, cap=None):
+        """Covariation evidence for every pair of columns of an alignment, on the device (sq_covariation_scan): rows = uint8
+        device tensor [R, L] of the rows' ASCII bytes.  Returns the device tensors (flat int64 = v * L + w, counts int32[P, 7] =
+        the rows of the pair types AU UA GC CG GU UG and the rows with a gap in both columns, cov int64[P]) of the cells
+        with w - v >= minspan, at least min_rows rows that hold a canonical pair and cov >= min_cov, unordered.  `cap`
+        (default 1 << 16) sizes the result buffers; the call is repeated with the true number when it was too small
+        (matrix_select's protocol).  Only that number comes to the host."""
+        import torch
+        L = _lib.load()
+        assert rows.dtype == torch.uint8 and rows.is_cuda and rows.dim() == 2 and rows.is_contiguous()
+        dev, R, Lcols = rows.device, int(rows.shape[0]), int(rows.shape[1])
+        cap = 1 << 16 if cap is None else int(cap)
+
+        def call(res, cap, out):                                   # (the entry has no status: out[1] stays 0)
+            _lib.check(L.sq_covariation_scan(_ptr(rows), R, Lcols, int(minspan), int(min_rows), int(min_cov), _ptr(scratch), nbytes,
+                                             _ptr(res[0]), _ptr(res[1]), _ptr(res[2]), cap, _ptr(out), _stream(dev)))
+
+        with torch.cuda.device(dev):
+            nbytes = int(L.sq_covariation_scratch(R, Lcols))
+            scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+            return _call_until_fits(dev, cap, (torch.int64, (torch.int32, 7), torch.int64), call, None)
+
+    def covariation_pairs(self, rows, pairs):
+        """The same numbers for given column pairs (sq_covariation_pairs): pairs = int32 device tensor [P, 2] of (v, w),
+        0 <= v < w < L.  Returns the device tensors (counts int32[P, 7], cov int64[P]) in the pairs' order; RuntimeError when
+        a pair is not such a pair.  Only the two result words come to the host."""
+        import torch
+        L = _lib.load()
+        assert rows.dtype == torch.uint8 and rows.is_cuda and rows.dim() == 2 and rows.is_contiguous()
+        assert pairs.dtype == torch.int32 and pairs.dim() == 2 and int(pairs.shape[1]) == 2 and pairs.device == rows.device
+        dev, R, Lcols, P = rows.device, int(rows.shape[0]), int(rows.shape[1]), int(pairs.shape[0])
+        pairs = pairs.contiguous()
+        with torch.cuda.device(dev):
+            nbytes = int(L.sq_covariation_scratch(R, Lcols))
+            scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+            counts = torch.empty((P, 7), dtype=torch.int32, device=dev)
+            cov = torch.empty(P, dtype=torch.int64, device=dev)
+            out = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.check(L.sq_covariation_pairs(_ptr(rows), R, Lcols, _ptr(pairs if P else None), P, _ptr(scratch), nbytes,
+                                              _ptr(counts if P else None), _ptr(cov if P else None), _ptr(out), _stream(dev)))
+            status = out.tolist()[1]
+        if status:
+            raise RuntimeError("sq_covariation_pairs: a pair is not 0 <= v < w < %d columns" % Lcols)
+        return counts, cov
 
     def score_tensors(self, recs, partner, row_start, row_rec):
         """ScoreStruct, stems and metrics of given structures on the device (sq_score_structs_dev; SQRNdbnseq.py:958-970,

@@ -127,6 +127,25 @@ static inline int sq_nussinov_threads(const SqMatchJob *jobs, int nj, int maxn, 
     return sq_mwm_crowd(jobs, nj, inflight) ? 64 : std::max(64, std::min(256, (maxn + 63) / 64 * 64));
 }
 
+// ---- the dynamic LDS of one Hungarian launch ----
+// Every block of a launch gets the same LDS, and every job must find room in it: the largest n and the largest m may belong
+// to different jobs.  need: the most a job wants for form a (sq_lsap.h); lds: what the launch gets -- that, or when it is
+// beyond a block's share of a CU, room for the vectors of the largest job alone (forms b, c).  Each job then takes the form
+// sq_lsap_form(n, m, lds) gives it.
+static const size_t SQ_LSAP_LDS_CAP = 150 * 1024;
+struct SqLsapLds { size_t need = 0, lds = 0; };
+static inline SqLsapLds sq_lsap_launch_lds(const SqMatchJob *h_jobs, int nj)
+{
+    SqLsapLds P;
+    int maxn = 0;
+    for (int q = 0; q < nj; q++) {
+        P.need = std::max(P.need, sq_lsap_lds_bytes(h_jobs[q].n, h_jobs[q].nedges));
+        maxn = std::max(maxn, (int)h_jobs[q].n);
+    }
+    P.lds = P.need <= SQ_LSAP_LDS_CAP ? P.need : std::min(sq_lsap_vec_bytes(maxn) + 64, SQ_LSAP_LDS_CAP);
+    return P;
+}
+
 // ---- launch order and size classes ----
 // what a job's place in the launch order is decided by: the dynamic LDS it needs (Nussinov: the waves of its block)
 static inline size_t sq_algo_lds_need(int algo, int n, int nedges)

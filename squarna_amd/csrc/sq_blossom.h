@@ -50,12 +50,6 @@
 #undef SQ_MWM_PROF2
 #endif
 
-#ifdef __HIPCC__
-#define SQ_HD __host__ __device__
-#else
-#define SQ_HD
-#endif
-
 // cross-lane helpers of the cooperative run(): one lane (host, tests) ...
 struct SqCoopSingle {
     SQ_HD int first_true(bool p, int nl) const { return p ? 0 : nl; }
@@ -70,6 +64,8 @@ struct SqCoopSingle {
     SQ_HD void min_pos_f64(double *p, double v) const { if (v < *p) *p = v; }
     SQ_HD void add_i32(int *p, int v) const { *p += v; }
     SQ_HD void min_i32_at(int *p, int v) const { if (v < *p) *p = v; }
+    SQ_HD void or_u32(uint32_t *p, uint32_t v) const { *p |= v; }
+    SQ_HD int fetch_add_i32(int *p, int v) const { const int o = *p; *p += v; return o; }
 };
 #ifdef __HIPCC__
 // ... or the 64 lanes of a wave.  first_true: lowest lane whose predicate holds (nl if none);
@@ -83,6 +79,8 @@ struct SqCoopWave {
     __device__ bool any(bool p) const { return __ballot(p) != 0; }
     __device__ void add_i32(int *p, int v) const { atomicAdd(p, v); }
     __device__ void min_i32_at(int *p, int v) const { atomicMin(p, v); }
+    __device__ void or_u32(uint32_t *p, uint32_t v) const { atomicOr(p, v); }
+    __device__ int fetch_add_i32(int *p, int v) const { return atomicAdd(p, v); }
     // *p = min(*p, v) for POSITIVE doubles (and +inf): their bit patterns order like unsigned integers
     __device__ void min_pos_f64(double *p, double v) const { atomicMin((unsigned long long *)p, (unsigned long long)__double_as_longlong(v)); }
     __device__ int first_true(bool p, int nl) const

@@ -1,4 +1,5 @@
-// sq_match.h -- job records of the on-device matching step (a-8, a-9, Nussinov).
+// sq_match.h -- job records of the on-device matching step (a-8, a-9, Nussinov); the layouts, byte counts and algorithms of the
+// Hungarian and Nussinov jobs come with it (sq_lsap.h, sq_nussinov.h, included below).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -20,29 +21,32 @@ struct SqMatchJob {
     int32_t next, pad;
 };
 
-// dynamic LDS of one Hungarian job: the row / column vectors (42 bytes per position) and the cost matrix in sparse form --
-// the matrix is zero except for the 2m stem cells: per row a bit mask of its non-zero columns with per-word prefix counts,
-// the edge ids of a row's cells in column order (16 bits each) and the m edge weights.  150 nt / 1,320 edges: 27 KB (the
-// dense form -- 16-bit ids for all n^2 cells -- took 62 KB, and LDS a job holds for its milliseconds is LDS the other
-// kernels on the chip do not get)
+// Host+device code of the matching step (sq_blossom.h, sq_lsap.h, sq_nussinov.h also compile with a plain C++ compiler for the
+// CPU tests).  SQ_HD_INLINE: the body of a kernel -- inlined before the optimiser runs, as if written into the kernel (the
+// Hungarian template took one VGPR more as an ordinary inline function).
 #ifdef __HIPCC__
 #define SQ_HD __host__ __device__
+#define SQ_HD_INLINE __host__ __device__ __forceinline__
+#define SQ_UNROLL _Pragma("unroll")
 #else
 #define SQ_HD
+#define SQ_HD_INLINE inline
+#define SQ_UNROLL
 #endif
-SQ_HD static inline size_t sq_lsap_vec_bytes(int n) { return ((size_t)n * (3 * 8 + 4 * 4 + 2) + 15) & ~(size_t)15; }
-SQ_HD static inline size_t sq_lsap_sparse_bytes(int n, int m)
+
+// The scratch and LDS layouts of the Hungarian and Nussinov kernels are carved array by array, as sq_algo_carve (sq_algo_plan.h)
+// carves the region of a chunk: the array starts at the next multiple of `align` bytes behind what `base` holds so far.
+// (Offsets, not pointers, are rounded: a pointer that went through an integer has lost its address space.)
+template <class T>
+SQ_HD static inline void sq_take(char *base, size_t &o, T *&a, size_t count, size_t align = alignof(T))
 {
-    const size_t nw = ((size_t)n + 31) / 32;
-    return (size_t)m * 8 + (size_t)n * nw * 4 + ((((size_t)n + 1) * 2 + 3) & ~(size_t)3) + (((size_t)n * nw * 2 + 3) & ~(size_t)3) + (size_t)m * 4 + 16;
+    o = (o + align - 1) & ~(align - 1);
+    a = reinterpret_cast<T *>(base + o);
+    o += count * sizeof(T);
 }
-SQ_HD static inline size_t sq_lsap_lds_bytes(int n, int m) { return sq_lsap_vec_bytes(n) + sq_lsap_sparse_bytes(n, m) + 64; }
-// global scratch of one Hungarian / Nussinov job (Edmonds: sq_mwm_scratch_bytes, sq_algo_plan.h)
-static inline size_t sq_lsap_scratch_bytes(int n) { return ((size_t)n * n + 3 * (size_t)n) * 8 + 4 * (size_t)n * 4 + 2 * (size_t)n + 64; }
-static inline size_t sq_nussinov_scratch_bytes(int n)
-{
-    return 2 * (size_t)n * n * 8 + (size_t)n * n * 4 + (((size_t)n * n + 15) & ~(size_t)15) + 4 * (size_t)(n + 2) * 4 + 64;
-}
+
+#include "sq_lsap.h"       // SqLsapLayout, sq_lsap_*_bytes, sq_lsap_form, sq_lsap_run
+#include "sq_nussinov.h"   // SqNussLayout, sq_nussinov_scratch_bytes, sq_nussinov_run
 
 // ---- records of the device-side RunAlgo (sq_algos_dev.hip) that the plan of a chunk (sq_algo_plan.h) sizes ----
 struct SqAlgoSize {                // per E / H / N job after its AnnotateStems pass (pinned, read by the host)

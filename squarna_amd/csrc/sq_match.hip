@@ -1,15 +1,10 @@
 // sq_match.hip -- a-8 / a-9 / Nussinov on device: the matching step of RunAlgo
 // (SQRNdbnseq.py:548-595) for the paramsets whose `algorithms` are H, E or N.
 //
-//   sq_lsap_kernel      Hungarian (SQRNalgos.py:113-135).  The reference calls
-//                       scipy.optimize.linear_sum_assignment (scipy 1.15.3, un-vendored C++:
-//                       Crouse 2016 shortest augmenting path).  Restated step by step -- same
-//                       column order, same tie-break towards unassigned columns -- so the
-//                       assignment is the one scipy returns, not just an optimal one.
-//                       One wave per job; the column scan of every augmentation step is
-//                       parallel over the lanes, everything else is scalar work on lane 0.
-//   sq_nussinov_kernel  Nussinov DP + BackTrack (SQRNalgos.py:6-93): anti-diagonal wavefront,
-//                       one block per job, fp64, first-best-k tie rule.
+//   sq_lsap_kernel      Hungarian (SQRNalgos.py:113-135): scipy's linear_sum_assignment restated
+//                       in sq_lsap.h, one wave per job.
+//   sq_nussinov_kernel  Nussinov DP + BackTrack (SQRNalgos.py:6-93) in sq_nussinov.h: the DP by
+//                       columns, one block per job, fp64, first-best-k tie rule.
 //   sq_mwm_kernel       Edmonds (SQRNalgos.py:96-110): networkx 3.4.2 max_weight_matching
 //                       restated in sq_blossom.h, one thread per job.
 #include <hip/hip_runtime.h>
@@ -26,182 +21,35 @@
 #include "sq_algo_plan.h"
 
 // ------------------------------------------------------------------------------------
-// LSAP: one wave per job.  Layout of the job's scratch (doubles then ints), nc = n:
-//   cost[n*n] u[n] v[n] spc[n] | path[n] col4row[n] row4col[n] remaining[n] | SR[n] SC[n] (bytes)
+// LSAP: one wave per job, the algorithm and the layout of the job's state in sq_lsap.h
 // ------------------------------------------------------------------------------------
+// the wave's barriers; with the vectors in global scratch (form c) lane 0's stores are released to the whole wave before the
+// next step's cross-lane reads, not left to same-wave store-to-load ordering through L1
+struct SqLsapBlockSync {
+    __device__ void operator()() const { __syncthreads(); }
+    __device__ void after_lane0(bool glob) const
+    {
+        if (glob) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __syncthreads();
+        if (glob) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+};
+
 extern "C" __global__ __launch_bounds__(64) void sq_lsap_kernel(const SqMatchJob *jobs, const SqMatchEdge *edges,
                                                                 char *scratch, int32_t *col4row_out, int lds_bytes)
 {
     extern __shared__ __attribute__((aligned(16))) char lsap_lds[];
     const SqMatchJob jb = jobs[blockIdx.x];
-    const int n = jb.n, lane = threadIdx.x;
+    const int n = jb.n, m = jb.nedges, lane = threadIdx.x;
     if (n <= 0) return;
-    double *cost = reinterpret_cast<double *>(scratch + jb.scratch_off);
-    double *u = cost + (size_t)n * n;
-    // the per-row/column vectors are touched in every step of the augmenting path: LDS when they fit
-    const size_t vec_bytes = sq_lsap_vec_bytes(n);
-    const bool vec_lds = vec_bytes + 64 <= (size_t)lds_bytes;
-    if (vec_lds) u = reinterpret_cast<double *>(lsap_lds);
-    double *v = u + n, *spc = v + n;
-    int32_t *path = reinterpret_cast<int32_t *>(spc + n);
-    int32_t *col4row = path + n, *row4col = col4row + n, *remaining = row4col + n;
-    uint8_t *SR = reinterpret_cast<uint8_t *>(remaining + n), *SC = SR + n;
-    // the cost matrix is zero except for the 2m stem cells: when it fits, LDS holds it in sparse form (sq_match.h) -- a step
-    // of the shortest-path scan never leaves the CU, and a zero cell costs one mask word
-    const int m = jb.nedges;
-    const int nw = (n + 31) >> 5;
-    const bool mat_lds = vec_lds && m < 32767 && vec_bytes + sq_lsap_sparse_bytes(n, m) + 64 <= (size_t)lds_bytes;
-    double *wts = reinterpret_cast<double *>(lsap_lds + vec_bytes);
-    uint32_t *mask = reinterpret_cast<uint32_t *>(wts + m);                                   // [n][nw] non-zero columns of a row
-    uint16_t *rowstart = reinterpret_cast<uint16_t *>(mask + (size_t)n * nw);                 // [n + 1] into cids
-    uint16_t *pre = rowstart + ((n + 1 + 1) & ~1);                                            // [n][nw] cells of the row in earlier words
-    uint16_t *cids = pre + (((size_t)n * nw + 1) & ~(size_t)1);                               // [2m] edge ids, row by row in column order
-
-    // mat = zeros; mat[v,w] = mat[w,v] = -(score**power)   (SQRNalgos.py:119-123)
-    if (mat_lds) {
-        for (int q = lane; q < n * nw; q += 64) mask[q] = 0u;
-    } else {
-        for (size_t q = lane; q < (size_t)n * n; q += 64) cost[q] = 0.0;
-    }
-    for (int q = lane; q < n; q += 64) { u[q] = 0.0; v[q] = 0.0; path[q] = -1; col4row[q] = -1; row4col[q] = -1; }
-    __syncthreads();
-    // (the cells of the stems are distinct, so the order of these writes does not matter)
-    if (mat_lds) {
-        for (int e = lane; e < m; e += 64) {
-            const SqMatchEdge ed = edges[jb.edge_off + e];
-            wts[e] = ed.weight;
-            atomicOr(&mask[ed.v * nw + (ed.w >> 5)], 1u << (ed.w & 31));
-            atomicOr(&mask[ed.w * nw + (ed.v >> 5)], 1u << (ed.v & 31));
-        }
-        __syncthreads();
-        // per-word prefix counts of every row, the rows' starts (a wave scan over chunks of rows)
-        const int per = (n + 63) / 64, r0 = min(lane * per, n), r1 = min(r0 + per, n);
-        int mine = 0;
-        for (int r = r0; r < r1; r++) {
-            int acc = 0;
-            for (int w = 0; w < nw; w++) { pre[r * nw + w] = (uint16_t)acc; acc += __popc(mask[r * nw + w]); }
-            mine += acc;
-        }
-        int inc = mine;
-        for (int off = 1; off < 64; off <<= 1) { const int y = __shfl_up(inc, off); if (lane >= off) inc += y; }
-        int run = inc - mine;
-        for (int r = r0; r < r1; r++) {
-            rowstart[r] = (uint16_t)run;
-            run += (int)pre[r * nw + nw - 1] + __popc(mask[r * nw + nw - 1]);
-        }
-        if (lane == 63) rowstart[n] = (uint16_t)inc;
-        __syncthreads();
-        for (int e = lane; e < m; e += 64) {
-            const SqMatchEdge ed = edges[jb.edge_off + e];
-            const int a = ed.v, c = ed.w;
-            cids[rowstart[a] + pre[a * nw + (c >> 5)] + __popc(mask[a * nw + (c >> 5)] & ((1u << (c & 31)) - 1u))] = (uint16_t)e;
-            cids[rowstart[c] + pre[c * nw + (a >> 5)] + __popc(mask[c * nw + (a >> 5)] & ((1u << (a & 31)) - 1u))] = (uint16_t)e;
-        }
-    } else {
-        for (int e = lane; e < m; e += 64) {
-            const SqMatchEdge ed = edges[jb.edge_off + e];
-            cost[(size_t)ed.v * n + ed.w] = -ed.weight;
-            cost[(size_t)ed.w * n + ed.v] = -ed.weight;
-        }
-    }
-    __syncthreads();
-
-    // The state of a path -- the row in hand, the columns left, the sink, the distance -- lives in registers: every lane
-    // takes lane 0's decision from the same broadcast reads (until late round 4 it went through four words of LDS and two
-    // barriers per step).  The scan of a step takes up to three columns per lane with the loads of one dependency level
-    // issued together (remaining -> mask word, v, shortest path, owner -> edge id -> weight).
-    for (int cur = 0; cur < n; cur++) {
-        // ---- augmenting_path(cur)
-        for (int q = lane; q < n; q += 64) { remaining[q] = n - q - 1; SR[q] = 0; SC[q] = 0; spc[q] = INFINITY; }
-        int i = cur, sink = -1, nrem = n;
-        double minval = 0.0;
-        __syncthreads();
-        while (sink == -1) {
-            const double ui = u[i];
-            const int rs_i = mat_lds ? (int)rowstart[i] : 0;
-            double lowest = INFINITY;
-            int first = -1, lastun = -1;
-            for (int it0 = 0; it0 < nrem; it0 += 192) {
-                int jj[3]; bool have[3];
-#pragma unroll
-                for (int t = 0; t < 3; t++) { const int it = it0 + 64 * t + lane; have[t] = it < nrem; jj[t] = remaining[have[t] ? it : 0]; }
-                uint32_t wd[3]; int pw[3], r4[3]; double vj[3], spj[3], cij[3];
-#pragma unroll
-                for (int t = 0; t < 3; t++) {
-                    const int j = jj[t];
-                    vj[t] = v[j]; spj[t] = spc[j]; r4[t] = row4col[j];
-                    if (mat_lds) { wd[t] = mask[i * nw + (j >> 5)]; pw[t] = (int)pre[i * nw + (j >> 5)]; cij[t] = 0.0; }
-                    else { wd[t] = 0u; pw[t] = 0; cij[t] = cost[(size_t)i * n + j]; }
-                }
-                if (mat_lds) {
-                    int cid[3];
-#pragma unroll
-                    for (int t = 0; t < 3; t++) {
-                        const int j = jj[t];
-                        const bool nz = (wd[t] >> (j & 31)) & 1u;
-                        cid[t] = nz ? (int)cids[rs_i + pw[t] + __popc(wd[t] & ((1u << (j & 31)) - 1u))] : -1;
-                    }
-#pragma unroll
-                    for (int t = 0; t < 3; t++) cij[t] = cid[t] >= 0 ? -wts[cid[t]] : 0.0;
-                }
-#pragma unroll
-                for (int t = 0; t < 3; t++) {                       // (a lane's columns in scan order)
-                    if (!have[t]) continue;
-                    const int it = it0 + 64 * t + lane, j = jj[t];
-                    const double r = minval + cij[t] - ui - vj[t];
-                    double sp = spj[t];
-                    if (r < sp) { path[j] = i; spc[j] = r; sp = r; }
-                    const bool un = r4[t] == -1;
-                    if (sp < lowest) { lowest = sp; first = it; lastun = un ? it : -1; }
-                    else if (sp == lowest && un) lastun = it;       // sequential rule: later unassigned ties win
-                }
-            }
-            // wave combine == the sequential scan over it = 0..nrem-1
-            // (DPP row shifts / broadcasts as in the blossom kernel: the three butterfly reductions over the LDS crossbar they
-            // replace -- 30 ds_bpermute per step of the path -- were the longest part of a step)
-            const double m = SqCoopWave::wave_min_f64(lowest);
-            const int f = SqCoopWave::wave_min_i32((lowest == m && first >= 0) ? first : 0x7fffffff);
-            const int lu = -SqCoopWave::wave_min_i32(-((lowest == m) ? lastun : -1));
-            minval = m;
-            if (m == INFINITY) { if (lane == 0) SR[i] = 1; sink = -2; break; }   // infeasible (cannot happen: finite costs)
-            const int index = lu >= 0 ? lu : f;
-            const int j = remaining[index], lastj = remaining[nrem - 1];
-            const int owner = row4col[j];
-            __syncthreads();                                        // (every lane has read what lane 0 overwrites)
-            if (lane == 0) { SR[i] = 1; SC[j] = 1; remaining[index] = lastj; }
-            nrem--;
-            if (owner == -1) sink = j; else i = owner;
-            // (the vectors may live in global scratch: lane 0's stores are released to the whole wave before the next step's
-            // cross-lane reads, not left to same-wave store-to-load ordering through L1)
-            if (!vec_lds) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __syncthreads();
-            if (!vec_lds) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        }
-        if (sink < 0) break;
-        // ---- dual update
-        if (lane == 0) u[cur] += minval;
-        for (int q = lane; q < n; q += 64) {
-            if (SR[q] && q != cur) u[q] += minval - spc[col4row[q]];
-            if (SC[q]) v[q] -= minval - spc[q];
-        }
-        __syncthreads();
-        // ---- augment
-        if (lane == 0) {
-            int j = sink;
-            for (;;) {
-                const int i2 = path[j];
-                row4col[j] = i2;
-                const int t = col4row[i2]; col4row[i2] = j; j = t;
-                if (i2 == cur) break;
-            }
-        }
-        __syncthreads();
-    }
-    for (int q = lane; q < n; q += 64) col4row_out[jb.out_off + q] = col4row[q];
+    const SqLsapForm form = sq_lsap_form(n, m, (size_t)lds_bytes);
+    const SqLsapLayout L = sq_lsap_carve(scratch + jb.scratch_off, lsap_lds, form, n, m);
+    sq_lsap_run<64>(L, form, n, m, edges + jb.edge_off, lane, SqLsapBlockSync(), SqCoopWave());
+    for (int q = lane; q < n; q += 64) col4row_out[jb.out_off + q] = L.col4row[q];
 }
 
 // ------------------------------------------------------------------------------------
-// Nussinov (SQRNalgos.py:44-93).  scratch: S[n*n] D[n*n] (doubles) | K[n*n] (int32) | has[n*n] (bytes)
+// Nussinov (SQRNalgos.py:44-93): one block per job, the algorithm and the layout of the job's scratch in sq_nussinov.h
 // out: pairs (k, j) appended to pairs_out[out_off..], count in count_out[job]
 // ------------------------------------------------------------------------------------
 extern "C" __global__ __launch_bounds__(256) void sq_nussinov_kernel(const SqMatchJob *jobs, const SqMatchEdge *edges,
@@ -214,126 +62,8 @@ extern "C" __global__ __launch_bounds__(256) void sq_nussinov_kernel(const SqMat
     int32_t *const my_count = count_out + (by_pad ? jb.pad : (int)blockIdx.x);
     // (n == 1: the column DP writes no cell, BackTrack would read K[0, 0] from reused scratch; the reference returns no pairs)
     if (n < 2) { if (tid == 0) *my_count = 0; return; }
-    double *S = reinterpret_cast<double *>(scratch + jb.scratch_off);   // region of n*n doubles: holds the column lists
-    double *D = S + (size_t)n * n;
-    int32_t *K = reinterpret_cast<int32_t *>(D + (size_t)n * n);
-    uint8_t *has = reinterpret_cast<uint8_t *>(K + (size_t)n * n);      // n*n bytes: BackTrack's "already queued" marks
-    const uint8_t *cd = codes + jb.pos_off;
-    // SCORES is sparse (the cells of the stems): per column j the list of (k, SCORES[(k, j)]) in ascending k,
-    // so a cell of the DP only visits the k that can pair with j (:73-74) instead of all of i..j-2
-    const int m = jb.nedges;
-    double *cs = S;                                                     // [m] scores
-    int32_t *ck = reinterpret_cast<int32_t *>(cs + m);                  // [m] row k
-    int32_t *col_off = ck + m, *cursor = col_off + (n + 1);            // [n + 1], [n]
-    // (the DP writes D and K of every cell above the main diagonal before anything reads them: only the diagonal of D and
-    // BackTrack's marks start at zero -- zeroing all three tables was 21 bytes per cell of traffic per job)
-    for (size_t q = tid; q < (size_t)n * n; q += nthr) has[q] = 0;
-    for (int q = tid; q < n; q += nthr) D[(size_t)q * n + q] = 0.0;
-    for (int q = tid; q <= n; q += nthr) col_off[q] = 0;
-    __syncthreads();
-    for (int e = tid; e < m; e += nthr) atomicAdd(&col_off[edges[jb.edge_off + e].w + 1], 1);
-    __syncthreads();
-    if (tid == 0) for (int j = 0; j < n; j++) col_off[j + 1] += col_off[j];
-    __syncthreads();
-    for (int q = tid; q < n; q += nthr) cursor[q] = col_off[q];
-    __syncthreads();
-    for (int e = tid; e < m; e += nthr) {                               // SCORES[(v,w)] = -stem[2]  (:49)
-        const SqMatchEdge ed = edges[jb.edge_off + e];
-        const int pos = atomicAdd(&cursor[ed.w], 1);
-        ck[pos] = ed.v; cs[pos] = -ed.weight;
-    }
-    __syncthreads();
-    for (int j = tid; j < n; j += nthr) {                               // ascending k inside every column (short lists)
-        const int a = col_off[j], b = col_off[j + 1];
-        for (int x = a + 1; x < b; x++) {
-            const int kk = ck[x]; const double vv = cs[x];
-            int y = x - 1;
-            while (y >= a && ck[y] > kk) { ck[y + 1] = ck[y]; cs[y + 1] = cs[y]; y--; }
-            ck[y + 1] = kk; cs[y + 1] = vv;
-        }
-    }
-    __syncthreads();
-    // The DP by COLUMNS (round 4; the reference and the kernel until then: by diagonals, :65-83).  Cell (i, j) reads
-    // D[i, k-1] (k <= j - 2), D[k+1, j-1] and D[i, j-1]: columns before j only, so the columns can be taken one after the
-    // other with all rows of a column at once -- the same values in any such order.  What the order buys: the list of
-    // column j -- the k that can pair with j, :73-74 -- is the same for every row (uniform loads, fetched while the column
-    // before is computed), D[k+1, j-1] is one value per list entry, and with D and K stored column-major the rows' reads of
-    // D[., k-1] and D[., j-1] are consecutive doubles.  By diagonals every cell chased column list -> k -> two cells of D
-    // through L2, three dependent trips per diagonal; now one per column.
-    // Dc[j * n + i] = D[i, j], Kc[j * n + i] = K[i, j].
-    double *const Dc = D;
-    int32_t *const Kc = K;
-    for (int j = 1; j < n; j++) {
-        const int x0 = col_off[j], x1 = col_off[j + 1];
-        const double *const dprevcol = Dc + (size_t)(j - 1) * n;
-        for (int i = tid; i < j; i += nthr) {
-            int bestk = -1; double best = 1e9;                          // :70
-            // k in range(i, j - 1) with (k, j) in SCORES, ascending (first best k, :77); four list entries per trip
-            for (int x = x0; x < x1; x += 4) {
-                int kk[4]; double d1[4], d2[4], cw[4]; bool ok[4];
-#pragma unroll
-                for (int t = 0; t < 4; t++) kk[t] = x + t < x1 ? ck[x + t] : 0x7fffffff;
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    ok[t] = kk[t] >= i && kk[t] < j - 1;
-                    d1[t] = 0.0; d2[t] = 0.0; cw[t] = 0.0;
-                    if (ok[t]) {
-                        // D[i, k-1] with k == i is numpy's D[i, -1] = D[i, n-1], which no cell has written yet at this point: 0 (:76)
-                        if (kk[t] > i) d1[t] = Dc[(size_t)(kk[t] - 1) * n + i];
-                        d2[t] = dprevcol[kk[t] + 1];
-                        cw[t] = cs[x + t];
-                    }
-                }
-#pragma unroll
-                for (int t = 0; t < 4; t++)
-                    if (ok[t]) {
-                        const double sc = d1[t] + d2[t] + cw[t];
-                        if (sc < best) { bestk = kk[t]; best = sc; }
-                    }
-                if (kk[3] >= j - 1) break;
-            }
-            const double dprev = dprevcol[i];                           // D[i, j-1] (i == j - 1: the diagonal, 0)
-            const bool take = best <= dprev;                            // :80-83
-            Kc[(size_t)j * n + i] = take ? bestk : -2;
-            Dc[(size_t)j * n + i] = take ? best : dprev;
-        }
-        __syncthreads();
-    }
-    // BackTrack(0, N-1) (:6-41): level-synchronous set of cells; one thread, O(N) cells
-    if (tid == 0) {
-        const int minloop = 3;
-        int32_t *out = pairs_out + 2 * (size_t)jb.out_off;
-        // queue storage: the tail of the job's scratch (two arrays of (i, j) cells)
-        int32_t *cur = reinterpret_cast<int32_t *>(has + (((size_t)n * n + 15) & ~(size_t)15)), *nxt = cur + 2 * (size_t)(n + 2);
-        uint8_t *inq = has;            // zeroed above
-        int qn = 1, np = 0;
-        cur[0] = 0; cur[1] = n - 1;
-        auto sep = [&](int p) { return cd[p] == 26 || cd[p] == 27; };
-        auto anysep = [&](int a, int b) { for (int x = a; x < b; x++) if (x >= 0 && x < n && sep(x)) return true; return false; };
-        while (qn) {
-            int nn = 0;
-            for (int t = 0; t < qn; t++) {
-                const int i = cur[2 * t], j = cur[2 * t + 1];
-                if (i < 0 || j < 0 || i >= n || j >= n) continue;
-                auto push = [&](int a, int b) {
-                    if (!inq[(size_t)a * n + b]) { inq[(size_t)a * n + b] = 1; nxt[2 * nn] = a; nxt[2 * nn + 1] = b; nn++; }
-                };
-                const int kk = Kc[(size_t)j * n + i];
-                if (kk != -2) {
-                    const int k = kk;
-                    if (((k - 1) - i > minloop) || ((k - 1) - i > 0 && anysep(i + 1, k - 1))) push(i, k - 1);
-                    if (((j - 1) - (k + 1) > minloop) || ((j - 1) - (k + 1) > 0 && anysep(k + 2, j - 1))) push(k + 1, j - 1);
-                    out[2 * np] = k; out[2 * np + 1] = j; np++;
-                } else {
-                    if (((j - 1) - i > minloop) || ((j - 1) - i > 0 && anysep(i + 1, j - 1))) push(i, j - 1);
-                }
-            }
-            for (int t = 0; t < nn; t++) inq[(size_t)nxt[2 * t] * n + nxt[2 * t + 1]] = 0;
-            for (int t = 0; t < 2 * nn; t++) cur[t] = nxt[t];
-            qn = nn;
-        }
-        *my_count = np;
-    }
+    sq_nussinov_run(sq_nuss_carve(scratch + jb.scratch_off, n, jb.nedges), n, jb.nedges, edges + jb.edge_off, codes + jb.pos_off,
+                    pairs_out + 2 * (size_t)jb.out_off, my_count, tid, nthr, [] { __syncthreads(); }, SqCoopWave());
 }
 
 // ------------------------------------------------------------------------------------
@@ -504,13 +234,9 @@ int sq_launch_matching(int algo, const SqMatchJob *h_jobs, int nj, const SqMatch
     int maxn = 0, maxm = 0;
     for (int q = 0; q < nj; q++) { maxn = maxn > h_jobs[q].n ? maxn : h_jobs[q].n; maxm = maxm > h_jobs[q].nedges ? maxm : h_jobs[q].nedges; }
     if (algo == 4) {                                     // SQ_ALGO_H
-        // LDS: the row/column vectors and, when it fits, the cost matrix in sparse form (sq_match.h); every job of the launch
-        // must find room: the largest n and the largest m may belong to different jobs
-        size_t lds = 0;
-        for (int q = 0; q < nj; q++) lds = std::max(lds, sq_lsap_lds_bytes(h_jobs[q].n, h_jobs[q].nedges));
-        if (lds > 64 * 1024) sq_max_dynamic_lds((const void *)sq_lsap_kernel, 150 * 1024);
-        if (lds > 150 * 1024) lds = sq_lsap_vec_bytes(maxn) + 64 < 150 * 1024 ? sq_lsap_vec_bytes(maxn) + 64 : 150 * 1024;   // vectors only
-        hipLaunchKernelGGL(sq_lsap_kernel, dim3(nj), dim3(64), lds, st, jobs, edges, d_scr, out, (int)lds);
+        const SqLsapLds P = sq_lsap_launch_lds(h_jobs, nj);
+        if (P.need > 64 * 1024) sq_max_dynamic_lds((const void *)sq_lsap_kernel, (int)SQ_LSAP_LDS_CAP);
+        hipLaunchKernelGGL(sq_lsap_kernel, dim3(nj), dim3(64), P.lds, st, jobs, edges, d_scr, out, (int)P.lds);
     } else if (algo == 2) {                              // SQ_ALGO_N
         const int nthr = sq_nussinov_threads(h_jobs, nj, maxn, inflight, kn);
         hipLaunchKernelGGL(sq_nussinov_kernel, dim3(nj), dim3(nthr), 0, st, jobs, edges, codes, d_scr, out, cnt, jobs_rw ? 1 : 0);

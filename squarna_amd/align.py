@@ -15,6 +15,7 @@ import numpy as np
 from .dbn import GAPS, SEPS, DBNToPairs, PairsToDBN, EncodedReactivities
 from .core import RunSQRNdbnseq
 from . import engine as _engine
+from .rows import offsets
 
 
 def ReAlignDict(shortseq, longseq):
@@ -148,8 +149,7 @@ def _consensus_bulk(structs, freqlimit):
     text = "".join(structs)
     raw = bracket_bytes(text)                                        # (one byte per character: the Cyrillic bracket letters recoded)
     L = _lib.load()
-    off = np.zeros(len(structs) + 1, np.int64)
-    np.cumsum([len(x) for x in structs], out=off[1:])
+    off = offsets([len(x) for x in structs])
     poff = np.zeros(len(structs) + 1, np.int64)
     rp = np.zeros(max(len(text), 2), np.int32)                      # (a line of n characters has at most n / 2 pairs)
     ptr = lambda a: ctypes.c_void_p(a.ctypes.data)

@@ -12,46 +12,16 @@ import io
 import os
 import sys
 
-from .config import ParseConfig, DATA_DIR
+from .config import DATA_DIR
 from .dbn import GAPS
 from .inputs import ParseInput
+from .options import alignment_defaults, batches, check_sources, configs_by_length, pick, prediction_options
 from .core import RunSQRNdbnseq, resolve_priority
 from . import engine as _engine
 
 #: records folded per GPU batch (bounded by the sum of N^2 as well)
 BATCH_RECORDS = 16384                 # records folded in one GPU batch (bigger batches: fewer, fuller kernel launches)
 BATCH_CELLS = 2 * 1024 * 1024 * 1024   # ... bounded by sum of N^2 x paramsets
-
-
-def _find_config(configfile, HOME_DIR, priority):
-    """(configuration file, whether the caller named one, priority names): SQUARNA.py:683-703.  No file named: def.conf (and, by
-    length, 500.conf / 1000.conf beside it) with the default priority paramsets."""
-    if configfile is None:
-        priority = set('bppN,bppH1,bppH2'.split(',')) if priority is None else {x for x in priority.split(',') if x}
-        return os.path.join(HOME_DIR, "def.conf"), False, priority
-    if not os.path.exists(configfile):
-        if os.path.exists(os.path.join(HOME_DIR, configfile + ".conf")):
-            configfile = os.path.join(HOME_DIR, configfile + ".conf")
-        elif os.path.exists(os.path.join(HOME_DIR, configfile)):
-            configfile = os.path.join(HOME_DIR, configfile)
-    assert os.path.exists(configfile), "Config file does not exist."
-    return configfile, True, set() if priority is None else {x for x in priority.split(',') if x}
-
-
-def _as_int(value, what, check, label):
-    try:
-        value = int(float(value))
-        assert check(value)
-        return value
-    except Exception:
-        raise ValueError("Inappropriate {} value ({}): {}".format(what, label, value))
-
-
-def _rank_keys(rankby):
-    """(rankbydiff, the order of the three scores) of a validated rankby string: SQUARNA.py:810-820."""
-    if "r" in rankby and "s" in rankby:
-        return "d" in rankby, (0, 2, 1)
-    return "d" in rankby, (2, 0, 1) if "r" in rankby else (1, 2, 0)
 
 
 def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, inputformat="qtrf",
@@ -68,11 +38,6 @@ def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
     """Print SQUARNA predictions for the given input (see SQUARNA.py:431-600 for the
     meaning of every parameter; short synonyms are accepted exactly as there)."""
     # synonyms, later ones win as in SQUARNA.py:602-664
-    def pick(cur, *alts):
-        for alt in alts:
-            if alt is not None:
-                cur = alt
-        return cur
     inputfile = pick(inputfile, i); fileformat = pick(fileformat, ff)
     configfile = pick(configfile, config, c); inputseq = pick(inputseq, seq, s)
     alignment = pick(alignment, ali, a); algorithms = pick(algorithms, algorithm, algo)
@@ -83,88 +48,25 @@ def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
     evalonly = pick(evalonly, eo); hardrest = pick(hardrest, hr); interchainonly = pick(interchainonly, ico)
     ignorewarn = pick(ignorewarn, ignore, iw); threads = pick(threads, t); byseq = pick(byseq, bs)
     verbose = pick(verbose, v)
-
-    if HOME_DIR is None:
-        HOME_DIR = DATA_DIR
     if write_to is None:
         write_to = sys.stdout
-    if inputfile != None and not os.path.exists(inputfile) and os.path.exists(os.path.join(HOME_DIR, inputfile)):
-        inputfile = os.path.join(HOME_DIR, inputfile)
 
-    # ---- validation (SQUARNA.py:677-808), same messages
-    assert os.path.exists(str(inputfile)) or inputseq, "Input file does not exist."
-    assert fileformat in {'unknown', 'fasta', 'default', 'stockholm', 'clustal'}, \
-        "Wrong fileformat, choose one of these: default,fasta,stockholm,clustal"
-    configfile, configfileset, priority = _find_config(configfile, HOME_DIR, priority)
-    if not configfileset:
-        configfile500 = os.path.join(HOME_DIR, "500.conf")
-        configfile1000 = os.path.join(HOME_DIR, "1000.conf")
-    assert ''.join(sorted(inputformat.replace('x', ''))) in {"q", "fq", "qr", "qt", "qrt", "fqr", "fqt", "fqrt"}, \
-        'Inappropriate inputformat value (subset of "fqrtx" with "q" being mandatory): {}'.format(inputformat)
-
-    maxstemnumset = maxstemnum is not None
-    maxstemnum = _as_int(maxstemnum, "maxstemnum", lambda x: x >= 0, "non-negative integer") if maxstemnumset else 10 ** 6
-    try:
-        threads = min(max(1, int(float(threads))), os.cpu_count())
-    except Exception:
-        raise ValueError("Inappropriate threads value (integer): {}".format(threads))
-    try:
-        M = float(M)
-    except Exception:
-        raise ValueError("Inappropriate M value (float): {}".format(M))
-    try:
-        B = float(B)
-    except Exception:
-        raise ValueError("Inappropriate B value (float): {}".format(B))
-    try:
-        algos = set(algorithms.upper())
-        assert algos <= {'E', 'G', 'H', 'N'}
-    except Exception:
-        raise ValueError('Inappropriate algorithm value (should be subset of "eghn"): {}'.format(algorithms))
-    assert rankby in {"r", "s", "rs", "dr", "ds", "drs"}, \
-        'Inappropriate rankby value (r/s/rs/dr/ds/drs): {}'.format(rankby)
-    outplimset = outplim is not None
-    if outplimset:
-        outplim = _as_int(outplim, "outplim", lambda x: x > 0, "positive integer")
-    toplim = _as_int(toplim, "toplim", lambda x: x > 0, "positive integer")
-    if not outplimset:
-        outplim = toplim
-    conslim = _as_int(conslim, "conslim", lambda x: x > 0, "positive integer")
-    poollim = _as_int(poollim, "poollim", lambda x: x > 0, "positive integer")
-    assert int(float(reactformat)) in {3, 10, 26}, "Inappropriate reactformat value (3/10/26): {}".format(reactformat)
-    reactformat = int(float(reactformat))
-    if levellimit is not None:
-        try:
-            levellimit = int(float(levellimit))
-        except Exception:
-            raise ValueError("Inappropriate levellimit value (integer): {}".format(levellimit))
-    try:
-        freqlimit = float(freqlimit)
-        assert 0 <= freqlimit <= 1
-    except Exception:
-        raise ValueError("Inappropriate freqlimit value (float between 0.0 and 1.0): {}".format(freqlimit))
-    try:
-        step3 = step3.lower()
-        assert step3 in {'u', 'i', '1', '2'}
-    except Exception:
-        raise ValueError("Inappropriate freqlimit value (float between 0.0 and 1.0): {}".format(step3))
-
-    rankbydiff, rankby = _rank_keys(rankby)
+    # ---- validation (SQUARNA.py:677-820), same messages: options.py
+    inputfile, configfile, configfileset, priority, HOME_DIR = check_sources(None, inputfile, inputseq, fileformat, configfile,
+                                                                             inputformat, HOME_DIR, priority)
+    opt = prediction_options(maxstemnum=maxstemnum, threads=threads, M=M, B=B, algorithms=algorithms, rankby=rankby,
+                             outplim=outplim, toplim=toplim, conslim=conslim, poollim=poollim, reactformat=reactformat,
+                             levellimit=levellimit, freqlimit=freqlimit, step3=step3)
+    threads, M, B, algos, rankbydiff, rankby = (opt[k] for k in ("threads", "M", "B", "algos", "rankbydiff", "rankby"))
+    outplim, toplim, conslim, poollim, reactformat = (opt[k] for k in ("outplim", "toplim", "conslim", "poollim", "reactformat"))
+    levellimit, freqlimit, step3 = opt["levellimit"], opt["freqlimit"], opt["step3"]
 
     if alignment and not configfileset:                          # SQUARNA.py:822-824
         configfile = os.path.join(HOME_DIR, "ali.conf")
     if rfam:
         raise NotImplementedError("Rfam restraint discovery (Infernal's cmscan, SQRNrfam.py) is out of scope of this build")
 
-    paramsetnames, paramsets = ParseConfig(configfile)
-    if not configfileset:
-        paramsetnames500, paramsets500 = ParseConfig(configfile500)
-        paramsetnames1000, paramsets1000 = ParseConfig(configfile1000)
-    if maxstemnumset:
-        sets = [paramsets] + ([paramsets500, paramsets1000] if not configfileset else [])
-        for group in sets:
-            for ps in group:
-                ps['maxstemnum'] = maxstemnum
+    config_for = configs_by_length(configfile, configfileset, HOME_DIR, opt["maxstemnum"])   # autoconfig, SQUARNA.py:868-878
 
     inputs, fmt, single_input = ParseInput(inputseq, inputfile, inputformat, fmt=fileformat,
                                            ignore=ignorewarn, inputrestr=inputrestr, M=M, B=B)
@@ -172,25 +74,15 @@ def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
         return [len(rec[1]) for rec in inputs]
     if alignment:                                                # SQUARNA.py:938-991
         from .align import RunSQRNdbnali
-        from .dbn import ReactDict, ProcessReacts
         defR, defS, defF = ParseInput(inputseq, inputfile, inputformat, returndefaults=True, fmt=fmt,
                                       ignore=ignorewarn, M=M, B=B)[0]
         objs = [obj for obj in inputs]
         N = len(objs[0][1])
         assert all(len(obj[1]) == N for obj in objs), 'The sequences are not aligned'
-        try:
-            if defR:
-                if len(defR) != N:
-                    defR = ProcessReacts(list(map(float, defR.split())), M=M, B=B)
-                else:
-                    defR = ProcessReacts([ReactDict[ch] for ch in defR], M=M, B=B)
-            assert not defR or len(defR) == N
-        except Exception:
-            raise ValueError('Inappropriate default reactivities line:\n {}'.format(defR))
-        assert not defS or len(defS) == N, 'Inappropriate default restraints line:\n {}'.format(defS)
-        assert not defF or len(defF) == N, 'Inappropriate default reference line:\n {}'.format(defF)
+        defR = alignment_defaults(defR, defS, defF, N, M, B)
         if levellimit is None:
             levellimit = 3 - int(N > 500)
+        paramsetnames, paramsets = config_for("")                # (ali.conf or the named configuration: not chosen by length)
         RunSQRNdbnali(objs, defR, defS, defF, levellimit, freqlimit, verbose, step3, paramsetnames, paramsets,
                       threads, rankbydiff, rankby, hardrest, interchainonly, toplim, outplim, conslim, reactformat,
                       poollim, entropy=entropy, algos=algos, sink=write_to, M=M, B=B)
@@ -205,15 +97,6 @@ def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
             found, rfamlabel = SearchG4RBP(inputs[0][1], g4, rbp)
             if found:
                 inputs[0][3] = found                             # (replaces any restraint line of the input)
-
-    def config_for(seq):                                        # autoconfig, SQUARNA.py:868-878
-        if configfileset:
-            return paramsetnames, paramsets
-        if len(seq) >= 1000:
-            return paramsetnames1000, paramsets1000
-        if len(seq) >= 500:
-            return paramsetnames500, paramsets500
-        return paramsetnames, paramsets
 
     eng = _engine.get_engine()
     common = dict(conslim=conslim, toplim=toplim, hardrest=hardrest, rankbydiff=rankbydiff, rankby=rankby,
@@ -295,17 +178,9 @@ def Predict(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
 def _predict_records(inputs, _select, config_for, flush):
     """The record loop of Predict's single-sequence mode: batches of records folded on the GPU, blocks printed in
     input order (the reference's ordered Pool.imap, SQUARNA.py:887-935)."""
-    batch, cells = [], 0
-    for index, (name, seq, reacts, restrs, ref) in enumerate(inputs):
-        if _select is not None and index not in _select:
-            continue
-        names, psets = config_for(seq)
-        batch.append((name, seq, reacts, restrs, ref, names, psets, index))
-        cells += len(seq) * len(seq) * len(psets)
-        if len(batch) >= BATCH_RECORDS or cells >= BATCH_CELLS:
-            flush(batch)
-            batch, cells = [], 0
-    if batch:
+    chosen = ((name, seq, reacts, restrs, ref) + config_for(seq) + (index,)
+              for index, (name, seq, reacts, restrs, ref) in enumerate(inputs) if _select is None or index in _select)
+    for batch in batches(chosen, lambda rec: len(rec[1]) * len(rec[1]) * len(rec[6]), BATCH_RECORDS, BATCH_CELLS):
         flush(batch)
 
 

@@ -10,6 +10,7 @@ from .dbn import DBNToPairs, encode_seq
 from .plan import workspace_size_class
 from .records import PackedRows
 from .results import unpack_result, _metrics, _MASK_IDS, _Blocks
+from .rows import offsets
 
 
 _STEM_DT = np.dtype([("i", "<i4"), ("j", "<i4"), ("len", "<i4"), ("reserved", "<i4"),
@@ -405,8 +406,7 @@ class Batch:
             text = "".join(dbns)
             if text.isascii():
                 # DBNToPairs (SQRNdbnseq.py:172-207) for all known structures in one library call (sq_dbn_pairs)
-                off = np.zeros(self.nseq + 1, np.int64)
-                np.cumsum([len(x) for x in dbns], out=off[1:])
+                off = offsets([len(x) for x in dbns])
                 poff = np.zeros(self.nseq + 1, np.int64)
                 rp = np.zeros(max(len(text), 2), np.int32)                  # (a line of n characters has at most n / 2 pairs)
                 _lib.check(self.L.sq_dbn_pairs(text.encode("ascii"), _ptr(off), self.nseq, _ptr(rp), len(rp) // 2, _ptr(poff)))

@@ -15,14 +15,14 @@ matrices.  ``Covariation`` prints nothing.
 """
 import contextlib
 import io
-import os
 
 import numpy as np
 
 from . import engine as _engine
-from .config import DATA_DIR
 from .dbn import DBNToPairs, GAPS
 from .inputs import ParseInput
+from .options import check_input
+from .results import TensorResult
 
 _DEVICE_METHODS = ("covariation_scan", "covariation_pairs")
 #: the six canonical pair types: columns 0..5 of ``CovariationResult.counts`` (column 6: the rows with a gap in both columns)
@@ -71,7 +71,7 @@ def _host_pairs(rows, pairs):
     return c.astype(np.int32), _cov_of(c).reshape(len(pairs))
 
 
-class CovariationResult:
+class CovariationResult(TensorResult):
     """What ``Covariation`` computes for an alignment of R rows and L columns.
 
     Host attributes: ``names``, ``sequences`` (as given), ``R``, ``L``, ``mode`` ("scan": every cell that passed the
@@ -82,6 +82,7 @@ class CovariationResult:
     pair), ``both_gap``, ``incompatible`` (R - bp_rows - both_gap), ``types`` (the pair types that occur)."""
 
     TYPES = TYPES
+    _TENSORS = ("cov", "pair_cols", "counts")
 
     def __init__(self, names, sequences, mode, source, pair_cols, counts, cov):
         self.names, self.sequences, self.R, self.L = names, sequences, len(sequences), len(sequences[0])
@@ -90,14 +91,6 @@ class CovariationResult:
 
     def __len__(self):
         return int(self.cov.numel())
-
-    @property
-    def device(self):
-        return self.cov.device
-
-    def cpu(self):
-        """The same result with every tensor in host memory."""
-        return CovariationResult(self.names, self.sequences, self.mode, self.source, self.pair_cols.cpu(), self.counts.cpu(), self.cov.cpu())
 
     @property
     def bp_rows(self):
@@ -162,11 +155,7 @@ class CovariationResult:
 
 def _read_alignment(inputfile, fileformat, inputformat, ignorewarn):
     """(names, sequences) of an alignment file, parsed as FoldAlignment parses it."""
-    if not os.path.exists(inputfile) and os.path.exists(os.path.join(DATA_DIR, inputfile)):
-        inputfile = os.path.join(DATA_DIR, inputfile)
-    assert os.path.exists(str(inputfile)), "Input file does not exist."
-    assert fileformat in {'unknown', 'fasta', 'default', 'stockholm', 'clustal'}, \
-        "Wrong fileformat, choose one of these: default,fasta,stockholm,clustal"
+    inputfile = check_input(None, inputfile, None, fileformat)[0]
     with contextlib.redirect_stdout(io.StringIO()):                  # (the parser announces a guessed file format)
         objs = [obj for obj in ParseInput(None, inputfile, inputformat, fmt=fileformat, ignore=ignorewarn)[0]]
     assert objs, "No input records."

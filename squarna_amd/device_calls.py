@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .rows import offsets
 
 #: the most blocks sq_variant_diff launches, four variants each at a time (SQ_VARIANT_MAX_BLOCKS, csrc/sq_variants.h)
 VARIANT_DIFF_MAX_BLOCKS = 2048
@@ -44,6 +45,15 @@ def _upload_once(arrays, device):
     return [dev[o:o + a.nbytes].view(getattr(torch, a.dtype.name)).reshape(a.shape) for a, o in zip(arrays, offs)]
 
 
+def _result_words(out, status_error):
+    """The two int64 words an entry leaves in `out`, read once: (records, status).  RuntimeError(status_error) on a status;
+    else the records' number."""
+    n, status = out.tolist()
+    if status:
+        raise RuntimeError(status_error)
+    return n
+
+
 def _call_until_fits(device, cap, dtypes, call, status_error):
     """The protocol of the entries that emit a number of records nobody knows beforehand (sq_colmatrix_select,
     sq_window_pair_count): result tensors of `cap` entries, one per dtype (a pair (dtype, n): `cap` rows of n), are allocated
@@ -58,9 +68,7 @@ def _call_until_fits(device, cap, dtypes, call, status_error):
                    for dt in dtypes]
         out = torch.zeros(2, dtype=torch.int64, device=device)
         call(tensors, cap, out)
-        n, status = out.tolist()
-        if status:
-            raise RuntimeError(status_error)
+        n = _result_words(out, status_error)
         if n <= cap:
             return tuple(t[:n] for t in tensors)
         cap = n
@@ -138,9 +146,7 @@ class DeviceCalls:
             out = torch.empty(2, dtype=torch.int64, device=dev)
             _lib.check(L.sq_align_pair_count(_ptr(partner), _ptr(cell_off), _ptr(d_off), _ptr(d_cols), nrec, int(Lcols), int(threshold),
                                              _ptr(scratch), nbytes, _ptr(flat), _ptr(count), _ptr(first), cap, _ptr(out), _stream(dev)))
-            n, status = out.tolist()
-        if status:
-            raise RuntimeError("sq_align_pair_count: a pair table entry lies outside its record or the %d columns" % Lcols)
+            n = _result_words(out, "sq_align_pair_count: a pair table entry lies outside its record or the %d columns" % Lcols)
         assert n <= cap
         return flat[:n], count[:n], first[:n]
 
@@ -187,9 +193,7 @@ class DeviceCalls:
             out = torch.empty(2, dtype=torch.int64, device=dev)
             _lib.check(_lib.load().sq_variant_diff(_ptr(partner), _ptr(cell_off), _ptr(lengths), int(rec0), nvar, _ptr(wt_rec), _ptr(pos_off),
                                                    int(Ltot), _ptr(diff), _ptr(pos_changed), _ptr(out), _stream(dev)))
-            status = out.tolist()[1]
-        if status:
-            raise RuntimeError("sq_variant_diff: a variant and its wild type differ in length or lie outside their tables or the %d "
+            _result_words(out, "sq_variant_diff: a variant and its wild type differ in length or lie outside their tables or the %d "
                                "positions, or a pair table entry is not a pair inside its row" % Ltot)
         return diff, pos_changed
 
@@ -221,9 +225,7 @@ class DeviceCalls:
                                                      _ptr(partner_d if ndup else None), _ptr(cell_off_d if ndup else None),
                                                      _ptr(lengths_d if ndup else None), ndup, _ptr(a_rec), _ptr(b_rec), _ptr(pos_off),
                                                      int(Ltot), _ptr(summary), _ptr(bound), _ptr(out), _stream(dev)))
-            status = out.tolist()[1]
-        if status:
-            raise RuntimeError("sq_duplex_summary: a duplex does not consist of its two chains and a separator column, a row lies "
+            _result_words(out, "sq_duplex_summary: a duplex does not consist of its two chains and a separator column, a row lies "
                                "outside its table or the %d positions, or a pair table entry is not a pair inside its row" % Ltot)
         return summary, bound
 
@@ -267,9 +269,7 @@ class DeviceCalls:
             out = torch.empty(2, dtype=torch.int64, device=dev)
             _lib.check(L.sq_covariation_pairs(_ptr(rows), R, Lcols, _ptr(pairs if P else None), P, _ptr(scratch), nbytes,
                                               _ptr(counts if P else None), _ptr(cov if P else None), _ptr(out), _stream(dev)))
-            status = out.tolist()[1]
-        if status:
-            raise RuntimeError("sq_covariation_pairs: a pair is not 0 <= v < w < %d columns" % Lcols)
+            _result_words(out, "sq_covariation_pairs: a pair is not 0 <= v < w < %d columns" % Lcols)
         return counts, cov
 
     def score_tensors(self, recs, partner, row_start, row_rec):
@@ -285,8 +285,7 @@ class DeviceCalls:
         L = _lib.load()
         dev, R, rows = partner.device, len(recs), len(row_rec)
         lens = np.array([rec.n for rec in recs], np.int64)
-        pos_off = np.zeros(R + 1, np.int64)
-        np.cumsum(lens, out=pos_off[1:])
+        pos_off = offsets(lens)
         cat = lambda parts, dt: np.concatenate([np.asarray(p, dt).reshape(-1) for p in parts] + [np.zeros(0, dt)])
         has_reacts = np.array([rec.reacts is not None for rec in recs], np.uint8)
         react_len = int(max((rec.n for rec in recs if rec.reacts is not None), default=0))
@@ -301,8 +300,7 @@ class DeviceCalls:
             assert int(arrays[7].min()) >= 0 and int((arrays[7] + width).max()) <= partner.numel(), "a row outside the partner tensor"
         gaps = any(rec.has_gap for rec in recs)
         if gaps:                                                     # (the maps between input columns and gap-free positions)
-            col_off = np.zeros(R + 1, np.int64)
-            np.cumsum([len(rec.colmap) for rec in recs], out=col_off[1:])
+            col_off = offsets([len(rec.colmap) for rec in recs])
             arrays += [col_off, cat([rec.colmap for rec in recs], np.int32), cat([rec.gfcol for rec in recs], np.int32)]
         with torch.cuda.device(dev):
             up = _upload_once([a if len(a) else np.zeros(1, a.dtype) for a in arrays], dev)

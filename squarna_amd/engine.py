@@ -23,6 +23,7 @@ from .records import Prepared, PackedRows  # noqa: F401
 from .batch import Batch, fold_concurrently
 from .device_calls import DeviceCalls, _upload_once
 from .results import unpack_result, packed_pair_tables, _Blocks, _BlockRun  # noqa: F401
+from .rows import offsets
 from .bpp import vienna_bpp, set_bpp_provider, bpp_terms, check_bpp_matrix  # noqa: F401
 from .plan import (pool_slots_wanted, pool_slots_wanted_many, pool_slot_cap, slot_bytes, default_structs,  # noqa: F401
                    MIN_CAND_PER_NT, SubBatchPlan, _kept_bytes_per_slot, _free_device_bytes, _shared_weights)
@@ -551,8 +552,7 @@ class HipEngine(DeviceCalls):
         if R and int(lens.max()) > 32768:
             k = int(lens.argmax())
             raise ValueError("entropy_tensors: record %d has %d nt; at most 32768 are supported" % (k, lens[k]))
-        pos_off = np.zeros(R + 1, np.int64)
-        np.cumsum(lens, out=pos_off[1:])
+        pos_off = offsets(lens)
         dev = torch.device("cuda", torch.cuda.current_device())
         L = _lib.load()
         lists = {}                                                   # (one list object per paramset: records that share it share the batch's job table)

@@ -11,9 +11,12 @@ import numpy as np
 from . import engine as _engine
 from . import fold as _fold
 from .dbn import gap_mask
+from .options import as_float, check_sources, configs_by_length, input_records, pick
+from .results import TensorResult
+from .rows import offsets
 
 
-class EntropyResult:
+class EntropyResult(TensorResult):
     """Row entropies of ``Entropy`` for R records.
 
     Host lists: ``names``, ``sequences`` (as given), ``paramset_names`` (per record: the paramset used).  ``source``: "device"
@@ -24,23 +27,16 @@ class EntropyResult:
     positions, separators counted -- the reference's value before it is rounded; NaN for a record without a position;
     ``nstems`` int32[R]: the stems that formed the matrix."""
 
+    _TENSORS = ("position", "lengths", "pos_off", "mean", "nstems")
+
     def __init__(self, names, sequences, paramset_names, tables, source):
         self.names, self.sequences, self.paramset_names, self.source = names, sequences, paramset_names, source
-        self.lengths, self.pos_off, self.position, self.mean, self.nstems = (tables[k] for k in _TENSORS)
+        self.position, self.lengths, self.pos_off, self.mean, self.nstems = (tables[k] for k in self._TENSORS)
         self._lengths = np.array([len(s) for s in sequences], np.int64)      # the host's copy of the sizes
-        self._pos_off = np.zeros(len(sequences) + 1, np.int64)
-        np.cumsum(self._lengths, out=self._pos_off[1:])
+        self._pos_off = offsets(self._lengths)
 
     def __len__(self):
         return len(self.names)
-
-    @property
-    def device(self):
-        return self.position.device
-
-    def cpu(self):
-        """The same result with every tensor in host memory."""
-        return EntropyResult(self.names, self.sequences, self.paramset_names, {k: getattr(self, k).cpu() for k in _TENSORS}, self.source)
 
     def row(self, r):
         """Record r's values, one per column of its sequence as given: a view of ``position``."""
@@ -59,9 +55,6 @@ class EntropyResult:
             rec = torch.repeat_interleave(torch.arange(R, device=self.device), self.lengths, output_size=total)
             out[rec, torch.arange(total, device=self.device) - self.pos_off[rec]] = self.position
         return out
-
-
-_TENSORS = ("lengths", "pos_off", "position", "mean", "nstems")
 
 
 def _stem_matrix(stem_matrix, on_device):
@@ -99,15 +92,14 @@ def Entropy(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
     The stems are ``AnnotateStems`` with no stem selected: every cell of a stem and its mirror hold the stem's total score,
     and row i with S = sum_j m[i][j] != 0 has H_i = -sum p log2 p over its nonzero cells, p = m[i][j] / S (else 0)."""
     import torch
-    pick = _fold._pick
     inputfile = pick(inputfile, i); fileformat = pick(fileformat, ff)
     configfile = pick(configfile, config, c); inputseq = pick(inputseq, seq, s)
     interchainonly = pick(interchainonly, ico); ignorewarn = pick(ignorewarn, ignore, iw)
-    inputfile, configfile, configfileset, _, HOME_DIR = _fold._check_sources(records, inputfile, inputseq, fileformat, configfile,
+    inputfile, configfile, configfileset, _, HOME_DIR = check_sources(records, inputfile, inputseq, fileformat, configfile,
                                                                              inputformat, HOME_DIR, None)
-    M, B = _fold._as_float(M, "M"), _fold._as_float(B, "B")
-    config_for = _fold._configs_by_length(configfile, configfileset, HOME_DIR)
-    inputs = _fold._input_records(records, inputseq, inputfile, inputformat, fileformat, ignorewarn, inputrestr, M, B)
+    M, B = as_float(M, "M"), as_float(B, "B")
+    config_for = configs_by_length(configfile, configfileset, HOME_DIR)
+    inputs = input_records(records, inputseq, inputfile, inputformat, fileformat, ignorewarn, inputrestr, M, B)
 
     eng = _engine.get_engine()
     if not hasattr(eng, "entropy_tensors"):
@@ -140,8 +132,7 @@ def Entropy(inputfile=None, fileformat="unknown", inputseq=None, configfile=None
     # gap-free coordinates -> columns of the sequences as given: NaN at the gap columns
     dev = t["position"].device
     lengths = np.array([len(sq) for sq in seqs], np.int64)
-    pos_off = np.zeros(len(seqs) + 1, np.int64)
-    np.cumsum(lengths, out=pos_off[1:])
+    pos_off = offsets(lengths)
     if (np.asarray(t["lengths"], np.int64) == lengths).all():
         position = t["position"]
     else:

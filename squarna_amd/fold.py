@@ -7,19 +7,17 @@ every record as torch tensors.  With the GPU engine the tables are formed by a k
 same object built on the CPU from its ``fold_records`` tuples.  ``Fold`` prints nothing.
 """
 import contextlib
-import io
-import os
 
 import numpy as np
 
 from . import api as _api
 from . import engine as _engine
 from .engine import _TABLES
-from .config import ParseConfig, DATA_DIR
 from .core import resolve_priority
 from .dbn import DBNToPairs, PairsToDBN, GAPS, SEPS, gap_mask
-from .inputs import ParseInput
-
+from .options import batches, check_sources, configs_by_length, input_records, pick, prediction_options
+from .results import TensorResult
+from .rows import offsets, partner_row, row_pairs
 
 
 def _seg_copy(torch, dst, dst_start, src, src_start, seg_len, colmap=None, map_start=None):
@@ -31,8 +29,7 @@ def _seg_copy(torch, dst, dst_start, src, src_start, seg_len, colmap=None, map_s
     if not total:
         return
     dev = src.device
-    cum = np.zeros(len(seg_len), np.int64)
-    np.cumsum(seg_len[:-1], out=cum[1:])
+    cum = offsets(seg_len)[:-1]
     cols = [dst_start, src_start - cum, cum, seg_len] + ([map_start] if colmap is not None else [])
     meta = torch.from_numpy(np.stack(cols)).to(dev)
     seg = torch.repeat_interleave(torch.arange(len(seg_len), device=dev), meta[3], output_size=total)
@@ -49,13 +46,10 @@ def _seg_copy(torch, dst, dst_start, src, src_start, seg_len, colmap=None, map_s
 
 def _offsets(nstruct, lengths):
     """(row_off, cell_off) of the tables' layout, int64[R + 1] each."""
-    row_off, cell_off = np.zeros(len(nstruct) + 1, np.int64), np.zeros(len(nstruct) + 1, np.int64)
-    np.cumsum(nstruct, out=row_off[1:])
-    np.cumsum((1 + nstruct) * lengths, out=cell_off[1:])
-    return row_off, cell_off
+    return offsets(nstruct), offsets((1 + nstruct) * lengths)
 
 
-class FoldResult:
+class FoldResult(TensorResult):
     """Predictions of ``Fold`` for R records.
 
     Host lists: ``names``, ``sequences`` (as given), ``paramset_names`` (per record: the names its mask bits stand for).
@@ -71,6 +65,8 @@ class FoldResult:
     Positions count the sequence AS GIVEN: gap columns are -1 and partners point at input columns, so ``dbn(r, k)`` is the
     string ``SQRNdbnseq`` returns."""
 
+    _TENSORS = _TABLES + ("lengths", "nstruct")
+
     def __init__(self, names, sequences, paramset_names, tables, nstruct, lengths, source):
         import torch
         self.names, self.sequences, self.paramset_names, self.source = names, sequences, paramset_names, source
@@ -83,15 +79,6 @@ class FoldResult:
     def __len__(self):
         return len(self.names)
 
-    @property
-    def device(self):
-        return self.partner.device
-
-    def cpu(self):
-        """The same result with every tensor in host memory."""
-        tables = {k: getattr(self, k).cpu() for k in _TABLES}
-        return FoldResult(self.names, self.sequences, self.paramset_names, tables, self._nstruct, self._lengths, self.source)
-
     def _row(self, r, k):
         """Row k of record r (0: the consensus) as a host int32 array."""
         if not 0 <= k <= self._nstruct[r]:
@@ -101,14 +88,11 @@ class FoldResult:
 
     def pairs(self, r, k):
         """Sorted (i, j) pairs, i < j, of structure k (0-based, rank order) of record r."""
-        row = self._row(r, k + 1)
-        i = np.flatnonzero(row > np.arange(len(row)))
-        return list(zip(i.tolist(), row[i].tolist()))
+        return row_pairs(self._row(r, k + 1))
 
     def _dbn(self, r, row):
         seq = self.sequences[r]
-        i = np.flatnonzero(row > np.arange(len(row)))
-        dbn = PairsToDBN(list(zip(i.tolist(), row[i].tolist())), len(seq))
+        dbn = PairsToDBN(row_pairs(row), len(seq))
         return ''.join(seq[q] if seq[q] in SEPS else ch for q, ch in enumerate(dbn)) if any(ch in SEPS for ch in seq) else dbn
 
     def dbn(self, r, k):
@@ -159,10 +143,7 @@ def _oracle_tables(results, seqs, keep):
     metrics = np.full((len(results), 16), np.nan)
 
     def row(dbn, n):
-        p = np.full(n, -1, np.int32)
-        for v, w in DBNToPairs(dbn):
-            p[v], p[w] = w, v
-        return p
+        return partner_row(DBNToPairs(dbn), n)
     for r, ((cons, preds, cm, bm), seq, ref) in enumerate(results):
         preds = preds[:keep]
         nstruct.append(len(preds))
@@ -204,13 +185,11 @@ def _join(parts, seqs):
         rows = 1 + ns
         rec = np.repeat(np.arange(len(idx)), rows)                   # one segment per row of partners
         j = np.arange(len(rec)) - np.repeat(np.cumsum(rows) - rows, rows)
-        src_cell = np.zeros(len(idx) + 1, np.int64)
-        np.cumsum(rows * ln, out=src_cell[1:])
+        src_cell = offsets(rows * ln)
         colmap = map_start = None
         if gapfree and any(short[k] != out_len[k] for k in idx):
             # where every gap-free position of the part's records lies in its input sequence
-            pos = np.zeros(len(idx) + 1, np.int64)
-            np.cumsum(ln, out=pos[1:])
+            pos = offsets(ln)
             cm = np.arange(int(pos[-1]), dtype=np.int64) - np.repeat(pos[:-1], ln)
             for q, k in enumerate(idx):
                 if short[k] != out_len[k]:
@@ -224,69 +203,6 @@ def _join(parts, seqs):
         metrics[torch.from_numpy(idx).to(dev)] = tables["metrics"]
     return dict(partner=partner, scores=scores, pset_mask=masks, metrics=metrics, row_off=torch.from_numpy(row_off).to(dev),
                 cell_off=torch.from_numpy(cell_off).to(dev)), nstruct, out_len
-
-
-def _pick(cur, *alts):
-    """A keyword's value: the last of its synonyms that was given, else the keyword itself."""
-    for alt in alts:
-        if alt is not None:
-            cur = alt
-    return cur
-
-
-def _check_sources(records, inputfile, inputseq, fileformat, configfile, inputformat, HOME_DIR, priority):
-    """Predict's checks of where the input and the configuration come from, same messages (SQUARNA.py:677-703):
-    (inputfile, configfile, whether the caller named one, priority names, HOME_DIR)."""
-    if HOME_DIR is None:
-        HOME_DIR = DATA_DIR
-    if inputfile != None and not os.path.exists(inputfile) and os.path.exists(os.path.join(HOME_DIR, inputfile)):
-        inputfile = os.path.join(HOME_DIR, inputfile)
-    assert records is not None or os.path.exists(str(inputfile)) or inputseq, "Input file does not exist."
-    assert fileformat in {'unknown', 'fasta', 'default', 'stockholm', 'clustal'}, \
-        "Wrong fileformat, choose one of these: default,fasta,stockholm,clustal"
-    configfile, configfileset, priority = _api._find_config(configfile, HOME_DIR, priority)
-    assert ''.join(sorted(inputformat.replace('x', ''))) in {"q", "fq", "qr", "qt", "qrt", "fqr", "fqt", "fqrt"}, \
-        'Inappropriate inputformat value (subset of "fqrtx" with "q" being mandatory): {}'.format(inputformat)
-    return inputfile, configfile, configfileset, priority, HOME_DIR
-
-
-def _as_float(value, what):
-    try:
-        return float(value)
-    except Exception:
-        raise ValueError("Inappropriate {} value (float): {}".format(what, value))
-
-
-def _configs_by_length(configfile, configfileset, HOME_DIR, maxstemnum=None):
-    """config_for(sequence) -> (paramset names, paramsets): the named configuration, or by length def / 500 / 1000
-    (autoconfig, SQUARNA.py:868-878)."""
-    configs = [ParseConfig(configfile)]
-    if not configfileset:
-        configs += [ParseConfig(os.path.join(HOME_DIR, "500.conf")), ParseConfig(os.path.join(HOME_DIR, "1000.conf"))]
-    if maxstemnum is not None:
-        for _, group in configs:
-            for ps in group:
-                ps['maxstemnum'] = maxstemnum
-
-    def config_for(sequence):
-        if configfileset or len(sequence) < 500:
-            return configs[0]
-        return configs[2] if len(sequence) >= 1000 else configs[1]
-    return config_for
-
-
-def _input_records(records, inputseq, inputfile, inputformat, fileformat, ignorewarn, inputrestr, M, B):
-    """The (name, sequence, reactivities, restraints, reference) tuples of `records` or of the parsed input."""
-    if records is not None:
-        inputs = [(">record{}".format(k + 1), rec, None, None, None) if isinstance(rec, str) else tuple(rec)
-                  for k, rec in enumerate(records)]
-        assert all(len(rec) == 5 for rec in inputs), "records: sequences or (name, sequence, reactivities, restraints, reference)"
-    else:
-        with contextlib.redirect_stdout(io.StringIO()):          # (the parser announces a guessed file format)
-            inputs = list(ParseInput(inputseq, inputfile, inputformat, fmt=fileformat, ignore=ignorewarn,
-                                     inputrestr=inputrestr, M=M, B=B)[0])
-    assert inputs, "No input records."
-    return inputs
 
 
 def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, inputformat="qtrf", maxstemnum=None,
@@ -313,7 +229,6 @@ def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, i
     their device; CPU tensors and arrays are uploaded once per record, not once per paramset.  The tensors are not modified.
     With an engine without ``fold_tensors`` the matrices go through the provider hook (``set_bpp_provider``) instead; records
     with the same sequence must then carry the same matrix."""
-    pick = _pick
     inputfile = pick(inputfile, i); fileformat = pick(fileformat, ff)
     configfile = pick(configfile, config, c); inputseq = pick(inputseq, seq, s)
     algorithms = pick(algorithms, algorithm, algo); rankby = pick(rankby, rb)
@@ -326,39 +241,19 @@ def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, i
         if flag:
             raise ValueError("Fold does not cover {}: use Predict".format(what))
 
-    # ---- validation: Predict's checks of the keywords both take, same messages (SQUARNA.py:677-808)
-    inputfile, configfile, configfileset, priority, HOME_DIR = _check_sources(records, inputfile, inputseq, fileformat, configfile,
-                                                                              inputformat, HOME_DIR, priority)
-    if maxstemnum is not None:
-        maxstemnum = _api._as_int(maxstemnum, "maxstemnum", lambda x: x >= 0, "non-negative integer")
-    M, B = _as_float(M, "M"), _as_float(B, "B")
-    try:
-        algos = set(algorithms.upper())
-        assert algos <= {'E', 'G', 'H', 'N'}
-    except Exception:
-        raise ValueError('Inappropriate algorithm value (should be subset of "eghn"): {}'.format(algorithms))
-    assert rankby in {"r", "s", "rs", "dr", "ds", "drs"}, 'Inappropriate rankby value (r/s/rs/dr/ds/drs): {}'.format(rankby)
-    if outplim is not None:
-        outplim = _api._as_int(outplim, "outplim", lambda x: x > 0, "positive integer")
-    toplim = _api._as_int(toplim, "toplim", lambda x: x > 0, "positive integer")
-    if outplim is None:
-        outplim = toplim
-    conslim = _api._as_int(conslim, "conslim", lambda x: x > 0, "positive integer")
-    poollim = _api._as_int(poollim, "poollim", lambda x: x > 0, "positive integer")
-    if levellimit is not None:
-        try:
-            levellimit = int(float(levellimit))
-        except Exception:
-            raise ValueError("Inappropriate levellimit value (integer): {}".format(levellimit))
-    rankbydiff, rankby = _api._rank_keys(rankby)
-
-    config_for = _configs_by_length(configfile, configfileset, HOME_DIR, maxstemnum)
-    inputs = _input_records(records, inputseq, inputfile, inputformat, fileformat, ignorewarn, inputrestr, M, B)
+    # ---- validation: Predict's checks of the keywords both take, same messages (SQUARNA.py:677-820): options.py
+    inputfile, configfile, configfileset, priority, HOME_DIR = check_sources(records, inputfile, inputseq, fileformat, configfile,
+                                                                             inputformat, HOME_DIR, priority)
+    opt = prediction_options(maxstemnum=maxstemnum, M=M, B=B, algorithms=algorithms, rankby=rankby, outplim=outplim,
+                             toplim=toplim, conslim=conslim, poollim=poollim, levellimit=levellimit)
+    M, B = opt["M"], opt["B"]
+    config_for = configs_by_length(configfile, configfileset, HOME_DIR, opt["maxstemnum"])
+    inputs = input_records(records, inputseq, inputfile, inputformat, fileformat, ignorewarn, inputrestr, M, B)
 
     eng = _engine.get_engine()
-    keep = max(int(outplim), 1)
-    common = dict(conslim=conslim, toplim=toplim, hardrest=hardrest, rankbydiff=rankbydiff, rankby=rankby,
-                  interchainonly=interchainonly, poollim=poollim, algos=algos, levellimit=levellimit, M=M, B=B, keep=keep)
+    keep = max(int(opt["outplim"]), 1)
+    common = dict(hardrest=hardrest, interchainonly=interchainonly, M=M, B=B, keep=keep,
+                  **{k: opt[k] for k in ("conslim", "toplim", "rankbydiff", "rankby", "poollim", "algos", "levellimit")})
     seqs = [rec[1] for rec in inputs]
     psnames = [config_for(sq)[0] for sq in seqs]
     parts = []
@@ -383,14 +278,8 @@ def Fold(inputfile=None, fileformat="unknown", inputseq=None, configfile=None, i
                         for r, k, rs in zip(res, idx, refsc)]
                 parts.append(_oracle_tables(full, [seqs[k] for k in idx], keep) + (idx, False, "host"))
 
-    batch, cells = [], 0
-    for k, sq in enumerate(seqs):                                # Predict's batches (api._predict_records)
-        batch.append(k)
-        cells += len(sq) * len(sq) * len(config_for(sq)[1])
-        if len(batch) >= _api.BATCH_RECORDS or cells >= _api.BATCH_CELLS:
-            flush(batch)
-            batch, cells = [], 0
-    if batch:
+    for batch in batches(range(len(seqs)), lambda k: len(seqs[k]) * len(seqs[k]) * len(config_for(seqs[k])[1]),
+                         _api.BATCH_RECORDS, _api.BATCH_CELLS):      # Predict's batches (api._predict_records)
         flush(batch)
     sources = {p[5] for p in parts}
     tables, nstruct, lengths = _join([p[:5] for p in parts], seqs)

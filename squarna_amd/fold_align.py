@@ -17,28 +17,16 @@ import os
 
 import numpy as np
 
-from . import api as _api
 from . import engine as _engine
 from . import align as _align
 from . import fold as _fold
-from .config import ParseConfig, DATA_DIR
-from .dbn import DBNToPairs, PairsToDBN, ProcessReacts, ReactDict, gap_mask
+from .dbn import DBNToPairs, PairsToDBN, gap_mask
 from .inputs import ParseInput
+from .options import alignment_defaults, check_sources, configs_by_length, pick, prediction_options
+from .results import TensorResult
+from .rows import checked_fit, first_fit, pair_table, partner_row, row_pairs
 
 _DEVICE_METHODS = ("stem_matrix", "matrix_select", "first_fit", "fold_tensors", "align_pair_count")
-
-
-def _partner_row(pairs, N):
-    row = np.full(N, -1, np.int32)
-    for v, w in pairs:
-        row[v], row[w] = w, v
-    return row
-
-
-def _row_pairs(row):
-    """Sorted (v, w) pairs, v < w, of a host partner row."""
-    v = np.flatnonzero(row > np.arange(len(row)))
-    return list(zip(v.tolist(), row[v].tolist()))
 
 
 def _consensus_order(torch, flat, count, first, nrows):
@@ -56,18 +44,7 @@ def _rank_cells(torch, idx, val):
     return idx[torch.sort(val[order], descending=True, stable=True)[1]]
 
 
-def _first_fit_host(cols, n):
-    """The sequential pass over the first n table rows on the host: [(v, w)] in the order taken."""
-    seen, res = set(), []
-    for v, w in cols[:n].tolist():
-        if v not in seen and w not in seen:
-            seen.add(v)
-            seen.add(w)
-            res.append((v, w))
-    return res
-
-
-class AlignmentResult:
+class AlignmentResult(TensorResult):
     """What alignment mode computes for an alignment of R rows and L columns.
 
     Host attributes: ``names``, ``sequences`` (as given), ``L``, the ``step3`` / ``freqlimit`` / ``levellimit`` the call
@@ -83,6 +60,9 @@ class AlignmentResult:
     TP FP FN FS PR RC of the three lines (NaN without a reference line).  ``react_scores`` float64[3] (0.5 without
     reactivities, as in the reference)."""
 
+    _TENSORS = ("steps", "stem_matrix", "pair_cols", "pair_count", "pair_first", "metrics", "react_scores")
+    _NESTED = ("rows",)
+
     def __init__(self, names, sequences, steps, stem_matrix, pair_cols, pair_count, pair_first, rows, metrics, react_scores, source,
                  step3, freqlimit, levellimit, lines, first_fit_rounds=()):
         self.names, self.sequences, self.L = names, sequences, len(sequences[0])
@@ -94,17 +74,6 @@ class AlignmentResult:
     def __len__(self):
         return len(self.names)
 
-    @property
-    def device(self):
-        return self.steps.device
-
-    def cpu(self):
-        """The same result with every tensor in host memory."""
-        t = [x.cpu() for x in (self.steps, self.stem_matrix, self.pair_cols, self.pair_count, self.pair_first)]
-        return AlignmentResult(self.names, self.sequences, *t, self.rows.cpu() if self.rows is not None else None, self.metrics.cpu(),
-                               self.react_scores.cpu(), self.source, self.step3, self.freqlimit, self.levellimit, self._lines,
-                               self.first_fit_rounds)
-
     def _step(self, step):
         if step not in (1, 2, 3):
             raise IndexError("steps are 1, 2 and 3")
@@ -112,7 +81,7 @@ class AlignmentResult:
 
     def pairs(self, step):
         """Sorted (v, w) column pairs, v < w, of the Step-`step` line."""
-        return _row_pairs(self._step(step))
+        return row_pairs(self._step(step))
 
     def dbn(self, step):
         """The dot-bracket line Predict prints for Step-`step` (as there, separator columns show '.')."""
@@ -144,21 +113,17 @@ class AlignmentResult:
         n = int((self.pair_count.double() >= float(freqlimit) * len(self.names)).sum())   # (a prefix: the counts only fall)
         if self.pair_cols.is_cuda and hasattr(eng, "first_fit"):
             flat = self.pair_cols[:n, 0].long() * self.L + self.pair_cols[:n, 1].long()
-            pairs = _row_pairs(_checked_fit(eng.first_fit(flat, self.L, 0), None))
+            pairs = row_pairs(_fitted_row(eng.first_fit(flat, self.L, 0), None))
         else:
-            pairs = _first_fit_host(self.pair_cols.cpu(), n)
+            pairs = first_fit(self.pair_cols[:n].tolist())
         dbn = PairsToDBN(list(set(pairs)), self.L)
         return dbn if levellimit is None else PairsToDBN(DBNToPairs(dbn), self.L, levellimit=levellimit)
 
 
-def _checked_fit(fit, rounds):
+def _fitted_row(fit, rounds):
     """The host's copy of a first fit's partner row (L int32: the only part of it that leaves the device)."""
     partner, info = fit
-    status, nrounds, npairs, live = info.tolist()
-    if status or live:
-        raise RuntimeError("sq_first_fit_dev: %d candidates still live after %d rounds" % (live, nrounds))
-    if rounds is not None:
-        rounds.append(nrounds)
+    checked_fit(info, rounds)
     return partner.cpu().numpy()
 
 
@@ -173,7 +138,7 @@ def _device_steps(eng, objs, defS, ps0, interchainonly, step3, freqlimit, fold_o
         recs = [(obj[1].upper().replace("T", "U"), obj[2], rests if rests else obj[3]) for obj in objs]
         smat = eng.stem_matrix(recs, ps0['bpweights'], ps0['minlen'], ps0['minbpscore'], interchainonly)
         idx, val = eng.matrix_select(smat, ps0['minbpscore'] * R, 4)
-        return _row_pairs(_checked_fit(eng.first_fit(_rank_cells(torch, idx, val), N, 4), rounds)), smat
+        return row_pairs(_fitted_row(eng.first_fit(_rank_cells(torch, idx, val), N, 4), rounds)), smat
 
     pairs, smat = iteration(defS)
     pairs1 = DBNToPairs(PairsToDBN(iteration(PairsToDBN(pairs, N))[0], N))   # iteration 2: the found line as restraints (:359-364)
@@ -188,23 +153,14 @@ def _device_steps(eng, objs, defS, ps0, interchainonly, step3, freqlimit, fold_o
     order = _consensus_order(torch, flat, count, first, R)
     flat, count, first = flat[order], count[order], first[order]
     n = int((count.double() >= freqlimit * R).sum())                 # :286 (a prefix: the counts only fall)
-    pairs2 = _row_pairs(_checked_fit(eng.first_fit(flat[:n], N, 0), rounds))
+    pairs2 = row_pairs(_fitted_row(eng.first_fit(flat[:n], N, 0), rounds))
     cols = torch.stack((flat // N, flat % N), 1).to(torch.int32)
     return pairs1, pairs2, smat, (cols, count, first), t, rounds
 
 
 def _host_table(rows, N):
     """(pair_cols, pair_count, pair_first) as numpy arrays from the consensus rows of a host FoldResult, in Consensus' order."""
-    partner, cell_off, lengths = rows.partner.numpy(), rows._cell_off, rows._lengths
-    keys, recs = [], []
-    for r in range(len(rows)):
-        row = partner[cell_off[r]:cell_off[r] + lengths[r]]
-        v = np.flatnonzero(row > np.arange(len(row)))
-        keys.append(v.astype(np.int64) * N + row[v])
-        recs.append(np.full(len(v), r, np.int64))
-    keys, recs = np.concatenate(keys), np.concatenate(recs)
-    uniq, at, counts = np.unique(keys, return_index=True, return_counts=True)
-    first = recs[at] if len(at) else np.zeros(0, np.int64)
+    uniq, counts, first = pair_table(rows.partner.numpy(), rows._cell_off, rows._lengths, N)
     order = np.lexsort((uniq, first, -counts))
     uniq, first, counts = uniq[order], first[order], counts[order]
     return np.stack((uniq // N, uniq % N), 1).astype(np.int32), counts.astype(np.int32), first.astype(np.int32)
@@ -233,7 +189,7 @@ def _host_steps(eng, objs, defR, defS, defF, ps0, interchainonly, step3, freqlim
     rows = _fold.FoldResult([obj[0] for obj in objs], seqs, [paramsetnames] * len(objs), tables, nstruct, lengths, "host")
     cols, count, first = _host_table(rows, N)
     n = int((count.astype(np.float64) >= freqlimit * len(objs)).sum())
-    pairs2 = _first_fit_host(cols, n)
+    pairs2 = first_fit(cols[:n].tolist())
     return pairs1, pairs2, torch.from_numpy(smat), tuple(torch.from_numpy(a) for a in (cols, count, first)), rows
 
 
@@ -251,12 +207,6 @@ def FoldAlignment(inputfile=None, fileformat="unknown", configfile=None, inputfo
     ``outplim`` (default: ``toplim``) bounds the structures kept per row in ``rows``.  ``verbose``, ``entropy`` and the
     ``rfam`` / ``g4`` / ``rbp`` restraint searches belong to ``Predict`` and raise ValueError here."""
     import torch
-
-    def pick(cur, *alts):
-        for alt in alts:
-            if alt is not None:
-                cur = alt
-        return cur
     inputfile = pick(inputfile, i); fileformat = pick(fileformat, ff)
     configfile = pick(configfile, config, c); algorithms = pick(algorithms, algorithm, algo)
     rankby = pick(rankby, rb); freqlimit = pick(freqlimit, freqlim, fl)
@@ -268,64 +218,16 @@ def FoldAlignment(inputfile=None, fileformat="unknown", configfile=None, inputfo
         if flag:
             raise ValueError("FoldAlignment does not cover {}: use Predict".format(what))
 
-    if HOME_DIR is None:
-        HOME_DIR = DATA_DIR
-    if inputfile != None and not os.path.exists(inputfile) and os.path.exists(os.path.join(HOME_DIR, inputfile)):
-        inputfile = os.path.join(HOME_DIR, inputfile)
-
-    # ---- validation: Predict's checks of the keywords both take, same messages (SQUARNA.py:677-808)
-    assert os.path.exists(str(inputfile)), "Input file does not exist."
-    assert fileformat in {'unknown', 'fasta', 'default', 'stockholm', 'clustal'}, \
-        "Wrong fileformat, choose one of these: default,fasta,stockholm,clustal"
-    configfile, configfileset, priority = _api._find_config(configfile, HOME_DIR, priority)
-    assert ''.join(sorted(inputformat.replace('x', ''))) in {"q", "fq", "qr", "qt", "qrt", "fqr", "fqt", "fqrt"}, \
-        'Inappropriate inputformat value (subset of "fqrtx" with "q" being mandatory): {}'.format(inputformat)
-    if maxstemnum is not None:
-        maxstemnum = _api._as_int(maxstemnum, "maxstemnum", lambda x: x >= 0, "non-negative integer")
-    try:
-        M = float(M)
-    except Exception:
-        raise ValueError("Inappropriate M value (float): {}".format(M))
-    try:
-        B = float(B)
-    except Exception:
-        raise ValueError("Inappropriate B value (float): {}".format(B))
-    try:
-        algos = set(algorithms.upper())
-        assert algos <= {'E', 'G', 'H', 'N'}
-    except Exception:
-        raise ValueError('Inappropriate algorithm value (should be subset of "eghn"): {}'.format(algorithms))
-    assert rankby in {"r", "s", "rs", "dr", "ds", "drs"}, 'Inappropriate rankby value (r/s/rs/dr/ds/drs): {}'.format(rankby)
-    if outplim is not None:
-        outplim = _api._as_int(outplim, "outplim", lambda x: x > 0, "positive integer")
-    toplim = _api._as_int(toplim, "toplim", lambda x: x > 0, "positive integer")
-    if outplim is None:
-        outplim = toplim
-    conslim = _api._as_int(conslim, "conslim", lambda x: x > 0, "positive integer")
-    poollim = _api._as_int(poollim, "poollim", lambda x: x > 0, "positive integer")
-    if levellimit is not None:
-        try:
-            levellimit = int(float(levellimit))
-        except Exception:
-            raise ValueError("Inappropriate levellimit value (integer): {}".format(levellimit))
-    try:
-        freqlimit = float(freqlimit)
-        assert 0 <= freqlimit <= 1
-    except Exception:
-        raise ValueError("Inappropriate freqlimit value (float between 0.0 and 1.0): {}".format(freqlimit))
-    try:
-        step3 = step3.lower()
-        assert step3 in {'u', 'i', '1', '2'}
-    except Exception:
-        raise ValueError("Inappropriate freqlimit value (float between 0.0 and 1.0): {}".format(step3))   # (the reference's text)
-    rankbydiff, rankby = _api._rank_keys(rankby)
-
+    # ---- validation: Predict's checks of the keywords both take, same messages (SQUARNA.py:677-820): options.py
+    inputfile, configfile, configfileset, priority, HOME_DIR = check_sources(None, inputfile, None, fileformat, configfile,
+                                                                             inputformat, HOME_DIR, priority)
+    opt = prediction_options(maxstemnum=maxstemnum, M=M, B=B, algorithms=algorithms, rankby=rankby, outplim=outplim,
+                             toplim=toplim, conslim=conslim, poollim=poollim, levellimit=levellimit, freqlimit=freqlimit,
+                             step3=step3)
+    M, B, levellimit, freqlimit, step3 = (opt[k] for k in ("M", "B", "levellimit", "freqlimit", "step3"))
     if not configfileset:                                            # SQUARNA.py:822-824
         configfile = os.path.join(HOME_DIR, "ali.conf")
-    paramsetnames, paramsets = ParseConfig(configfile)
-    if maxstemnum is not None:
-        for ps in paramsets:
-            ps['maxstemnum'] = maxstemnum
+    paramsetnames, paramsets = configs_by_length(configfile, True, HOME_DIR, opt["maxstemnum"])("")
 
     with contextlib.redirect_stdout(io.StringIO()):                  # (the parser announces a guessed file format)
         inputs, fmt, _ = ParseInput(None, inputfile, inputformat, fmt=fileformat, ignore=ignorewarn, M=M, B=B)
@@ -334,24 +236,14 @@ def FoldAlignment(inputfile=None, fileformat="unknown", configfile=None, inputfo
     assert objs, "No input records."
     N = len(objs[0][1])                                              # SQUARNA.py:938-991
     assert all(len(obj[1]) == N for obj in objs), 'The sequences are not aligned'
-    try:
-        if defR:
-            if len(defR) != N:
-                defR = ProcessReacts(list(map(float, defR.split())), M=M, B=B)
-            else:
-                defR = ProcessReacts([ReactDict[ch] for ch in defR], M=M, B=B)
-        assert not defR or len(defR) == N
-    except Exception:
-        raise ValueError('Inappropriate default reactivities line:\n {}'.format(defR))
-    assert not defS or len(defS) == N, 'Inappropriate default restraints line:\n {}'.format(defS)
-    assert not defF or len(defF) == N, 'Inappropriate default reference line:\n {}'.format(defF)
+    defR = alignment_defaults(defR, defS, defF, N, M, B)
     if levellimit is None:
         levellimit = 3 - int(N > 500)
 
     eng = _engine.get_engine()
-    keep = max(int(outplim), 1)
-    fold_opts = dict(conslim=conslim, toplim=toplim, hardrest=hardrest, rankbydiff=rankbydiff, rankby=rankby,
-                     interchainonly=interchainonly, poollim=poollim, algos=algos, M=M, B=B)
+    keep = max(int(opt["outplim"]), 1)
+    fold_opts = dict(hardrest=hardrest, interchainonly=interchainonly, M=M, B=B,
+                     **{k: opt[k] for k in ("conslim", "toplim", "rankbydiff", "rankby", "poollim", "algos")})
     names, seqs = [obj[0] for obj in objs], [obj[1] for obj in objs]
     rows, rounds = None, ()
     on_device = all(hasattr(eng, m) for m in _DEVICE_METHODS) and not hasattr(eng, "reduce_matrix")
@@ -385,7 +277,7 @@ def FoldAlignment(inputfile=None, fileformat="unknown", configfile=None, inputfo
                 step1pairs.append((v, w))
         step3dbn = PairsToDBN(sorted(step1pairs), N)
     lines = (step1dbn, step2dbn, step3dbn)
-    steps = np.stack([_partner_row(DBNToPairs(line), N) for line in lines])
+    steps = np.stack([partner_row(DBNToPairs(line), N) for line in lines])
     metrics = np.array([[float(x) for x in _align.Metrics(defF, line)] for line in lines], np.float64)
     reacts = np.array([float(_align.ReactScore(defR, seqs[0], line)) for line in lines], np.float64)
     if table is None:

@@ -18,6 +18,9 @@ import numpy as np
 from . import engine as _engine
 from . import fold as _fold
 from .dbn import GAPS, SEPS
+from .options import derived_inputs, pick
+from .results import TensorResult
+from .rows import position_axis
 
 _DEVICE_METHODS = ("fold_tensors", "duplex_summary")
 #: the columns of ``DuplexResult.summary``
@@ -27,20 +30,19 @@ _FOLD_INPUTS = ("records", "inputfile", "inputseq", "inputrestr", "i", "s", "seq
 
 
 def _side(what, filekey, records, inputfile, inputformat, fileformat, ignorewarn, M, B, kw):
-    """The (name, sequence, reactivities, restraints, reference) tuples of one side, checked: no chain boundary inside."""
+    """One side's (name, sequence, reactivities, restraints, reference) tuples, checked: no chain boundary inside; and the
+    keywords for Fold."""
     if records is not None and inputfile is not None:
         raise ValueError("FoldDuplex: {} and {} are both given; one of them is needed".format(what, filekey))
-    inputfile = _fold._check_sources(records, inputfile, None, fileformat, kw.get("configfile"), inputformat, kw.get("HOME_DIR"),
-                                     kw.get("priority"))[0]
-    recs = _fold._input_records(list(records) if records is not None else None, None, inputfile, inputformat, fileformat, ignorewarn,
-                                None, M, B)
+    recs, kw = derived_inputs("FoldDuplex", list(records) if records is not None else None, inputfile, None, inputformat,
+                              fileformat, ignorewarn, M, B, kw)
     for name, seq, reacts, rests, _ in recs:
         if any(ch in GAPS or ch in SEPS for ch in seq):
             raise ValueError("FoldDuplex: the sequence of record {} of the {} holds a gap or separator character: a chain "
                              "boundary inside an input would make \"the other chain\" ambiguous".format(name, what))
         if isinstance(reacts, str):
             raise ValueError("FoldDuplex: the reactivities of record {} of the {} are a string; a list of numbers is needed".format(name, what))
-    return recs
+    return recs, kw
 
 
 def _pair_lists(pairs, T, Q, homodimers):
@@ -110,7 +112,7 @@ def _host_summary(solos, folds, a_rec, b_rec, pos_off):
     return summary, bound
 
 
-class DuplexResult:
+class DuplexResult(TensorResult):
     """What ``FoldDuplex`` computes for T targets, Q queries and P duplexes.
 
     Host attributes: ``target_names``, ``query_names``, ``target_sequences``, ``query_sequences`` (the queries' lists are
@@ -126,6 +128,7 @@ class DuplexResult:
     in either role; record r starts at pos_off[r]."""
 
     _TENSORS = ("a_rec", "b_rec", "pos_off", "summary", "bound")
+    _NESTED = ("solos", "folds")
 
     def __init__(self, target_names, query_names, target_sequences, query_sequences, self_screen, source, solos, folds, a_rec, b_rec,
                  pos_off, summary, bound):
@@ -139,16 +142,6 @@ class DuplexResult:
 
     def __len__(self):
         return len(self._a)
-
-    @property
-    def device(self):
-        return self.summary.device
-
-    def cpu(self):
-        """The same result with every tensor in host memory."""
-        return DuplexResult(self.target_names, self.query_names, self.target_sequences, self.query_sequences, self.self_screen,
-                            self.source, self.solos.cpu(), self.folds.cpu() if self.folds is not None else None,
-                            *(getattr(self, k).cpu() for k in self._TENSORS))
 
     def _duplex(self, k):
         if not 0 <= k < len(self._a):
@@ -266,34 +259,24 @@ def FoldDuplex(targets=None, queries=None, pairs=None, homodimers=False, targetf
     (validation and messages are ``Fold``'s).  A record's structure is its consensus row.  ``bpp`` raises ValueError: a
     chain's matrix is not its duplexes'."""
     import torch
-    pick = _fold._pick
     kw = dict(fold_keywords)
-    fileformat = pick(fileformat, kw.pop("ff", None)); ignorewarn = pick(ignorewarn, kw.pop("ignore", None), kw.pop("iw", None))
     interchainonly = pick(kw.pop("interchainonly", False), kw.pop("ico", None))
-    if kw.get("bpp") is not None:
-        raise ValueError("FoldDuplex does not cover bpp: use Fold")
     for key in _FOLD_INPUTS:
         if kw.get(key) is not None:
             raise ValueError("FoldDuplex takes its input as targets / queries (targetfile / queryfile), not as {}".format(key))
         kw.pop(key, None)
-    M, B = _fold._as_float(M, "M"), _fold._as_float(B, "B")
-    trecs = _side("targets", "targetfile", targets, targetfile, inputformat, fileformat, ignorewarn, M, B, kw)
+    trecs, common = _side("targets", "targetfile", targets, targetfile, inputformat, fileformat, ignorewarn, M, B, kw)
     self_screen = queries is None and queryfile is None
-    qrecs = [] if self_screen else _side("queries", "queryfile", queries, queryfile, inputformat, fileformat, ignorewarn, M, B, kw)
+    qrecs = [] if self_screen else _side("queries", "queryfile", queries, queryfile, inputformat, fileformat, ignorewarn, M, B, kw)[0]
     T, Q = len(trecs), len(qrecs)
     a, b = _pair_lists(pairs, T, None if self_screen else Q, bool(homodimers))
 
     # ---- the solo records on one axis, the duplex records
     srecs = [tuple(rec) for rec in trecs + qrecs]
     a_rec, b_rec = a, b + (0 if self_screen else T)
-    pos_off = np.zeros(T + Q + 1, np.int64)
-    np.cumsum([len(rec[1]) for rec in srecs], out=pos_off[1:])
-    Ltot = int(pos_off[-1])
-    if Ltot >= 2 ** 31:
-        raise ValueError("{} positions in all records: fewer than 2^31 are needed".format(Ltot))
+    pos_off, Ltot = position_axis([rec[1] for rec in srecs])
     drecs = [_duplex_record(srecs[p], srecs[q]) for p, q in zip(a_rec.tolist(), b_rec.tolist())]
 
-    common = dict(inputformat=inputformat, ignorewarn=ignorewarn, M=M, B=B, **kw)
     solos = _fold.Fold(records=srecs, interchainonly=False, **common)
     folds = _fold.Fold(records=drecs, interchainonly=interchainonly, **common) if drecs else None
 

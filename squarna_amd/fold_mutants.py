@@ -17,6 +17,9 @@ import numpy as np
 from . import engine as _engine
 from . import fold as _fold
 from .dbn import GAPS, SEPS
+from .options import derived_inputs
+from .results import TensorResult
+from .rows import position_axis
 
 _DEVICE_METHODS = ("fold_tensors", "variant_diff")
 
@@ -130,7 +133,7 @@ def _host_diff(folds, R, wt_rec, pos_off):
     return diff, pos_changed
 
 
-class MutantResult:
+class MutantResult(TensorResult):
     """What ``FoldMutants`` computes for R records with V variants of S substitution sites in all.
 
     Host attributes: ``names``, ``sequences`` (the wild types'), ``mode`` ("scan" or "explicit"), ``source`` ("device" or
@@ -145,6 +148,7 @@ class MutantResult:
     variants changed that position's partner; record r starts at pos_off[r]."""
 
     _TENSORS = ("pos_off", "var_off", "site_off", "site_pos", "site_letter", "diff", "pos_changed")
+    _NESTED = ("folds",)
 
     def __init__(self, names, sequences, mode, source, folds, pos_off, var_off, site_off, site_pos, site_letter, diff, pos_changed):
         self.names, self.sequences, self.mode, self.source, self.folds = names, sequences, mode, source, folds
@@ -155,15 +159,6 @@ class MutantResult:
 
     def __len__(self):
         return len(self.names)
-
-    @property
-    def device(self):
-        return self.diff.device
-
-    def cpu(self):
-        """The same result with every tensor in host memory."""
-        return MutantResult(self.names, self.sequences, self.mode, self.source, self.folds.cpu(),
-                            *(getattr(self, k).cpu() for k in self._TENSORS))
 
     def _block(self, r, k=None):
         """The variants [lo, hi) of record r, or the one place of its variant k."""
@@ -245,27 +240,14 @@ def FoldMutants(inputfile=None, inputseq=None, records=None, positions=None, var
     and messages are ``Fold``'s).  A record's structure is its consensus row.  ``bpp`` raises ValueError: a wild type's
     matrix is not its variants'."""
     import torch
-    pick = _fold._pick
-    kw = dict(fold_keywords)
-    inputfile = pick(inputfile, kw.pop("i", None)); inputseq = pick(inputseq, kw.pop("seq", None), kw.pop("s", None))
-    fileformat = pick(fileformat, kw.pop("ff", None)); ignorewarn = pick(ignorewarn, kw.pop("ignore", None), kw.pop("iw", None))
-    if kw.get("bpp") is not None:
-        raise ValueError("FoldMutants does not cover bpp: use Fold")
     if variants is not None and positions is not None:
         raise ValueError("FoldMutants: positions belong to a scan; with variants given they must be None")
-    M, B = _fold._as_float(M, "M"), _fold._as_float(B, "B")
-    inputfile = _fold._check_sources(records, inputfile, inputseq, fileformat, kw.get("configfile"), inputformat,
-                                     kw.get("HOME_DIR"), kw.get("priority"))[0]
-    inputs = _fold._input_records(records, inputseq, inputfile, inputformat, fileformat, ignorewarn, kw.pop("inputrestr", None), M, B)
+    inputs, kw = derived_inputs("FoldMutants", records, inputfile, inputseq, inputformat, fileformat, ignorewarn, M, B, fold_keywords)
 
     # ---- the variants
     names, seqs = [rec[0] for rec in inputs], [rec[1] for rec in inputs]
     R = len(inputs)
-    pos_off, var_off = np.zeros(R + 1, np.int64), np.zeros(R + 1, np.int64)
-    np.cumsum([len(s) for s in seqs], out=pos_off[1:])
-    Ltot = int(pos_off[-1])
-    if Ltot >= 2 ** 31:
-        raise ValueError("{} positions in all records: fewer than 2^31 are needed".format(Ltot))
+    (pos_off, Ltot), var_off = position_axis(seqs), np.zeros(R + 1, np.int64)
     if variants is None:
         scan = _scan_positions(positions, min(len(s) for s in seqs))
     else:
@@ -293,7 +275,7 @@ def FoldMutants(inputfile=None, inputseq=None, records=None, positions=None, var
     site_off = np.concatenate([np.zeros(1, np.int64)] + offs)
     wt_rec = np.repeat(np.arange(R), np.diff(var_off))
 
-    folds = _fold.Fold(records=[tuple(rec) for rec in inputs] + vrecs, inputformat=inputformat, ignorewarn=ignorewarn, M=M, B=B, **kw)
+    folds = _fold.Fold(records=[tuple(rec) for rec in inputs] + vrecs, **kw)
     assert folds._lengths[R:].tolist() == folds._lengths[wt_rec].tolist(), "a variant's table does not have its wild type's length"
 
     eng = _engine.get_engine()

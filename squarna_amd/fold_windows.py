@@ -18,7 +18,9 @@ from . import align as _align
 from . import engine as _engine
 from . import fold as _fold
 from .dbn import GAPS, SEPS, PairsToDBN
-from .fold_align import _row_pairs
+from .options import as_freqlimit, derived_inputs
+from .results import TensorResult
+from .rows import checked_fit, first_fit, offsets, pair_table, partner_row, position_axis, row_pairs
 
 _DEVICE_METHODS = ("fold_tensors", "window_pair_count", "first_fit")
 
@@ -48,15 +50,11 @@ def _rank_order(xp, rec, freq, count, first, flat, nwin):
 
 def _first_fit_host(flat, Ltot):
     """The sequential pass over ranked candidates gi * Ltot + gj on the host: the partner row of the whole axis."""
-    partner = np.full(Ltot, -1, np.int32)
-    for f in flat.tolist():
-        v, w = divmod(f, Ltot)
-        if partner[v] < 0 and partner[w] < 0:
-            partner[v], partner[w] = w, v
-    return partner
+    v, w = np.divmod(flat, Ltot)
+    return partner_row(first_fit(zip(v.tolist(), w.tolist())), Ltot)
 
 
-class WindowResult:
+class WindowResult(TensorResult):
     """What ``FoldWindows`` computes for R records cut into T windows.
 
     Host attributes: ``names``, ``sequences``, ``window``, ``step``, ``freqlimit``, ``source`` ("device" or "host": where the
@@ -79,23 +77,14 @@ class WindowResult:
         self.pair_pos, self.pair_count, self.pair_cover, self.pair_first = pair_pos, pair_count, pair_cover, pair_first
         self.consensus, self.metrics = consensus, metrics
         # the host's copy of the sizes: the helpers below index with it
-        self._pos_off = np.zeros(len(sequences) + 1, np.int64)
-        np.cumsum([len(s) for s in sequences], out=self._pos_off[1:])
+        self._pos_off = offsets([len(s) for s in sequences])
         self._pair_off = None
 
     _TENSORS = ("pos_off", "win_off", "starts", "pair_off", "pair_pos", "pair_count", "pair_cover", "pair_first", "consensus", "metrics")
+    _NESTED = ("windows",)
 
     def __len__(self):
         return len(self.names)
-
-    @property
-    def device(self):
-        return self.consensus.device
-
-    def cpu(self):
-        """The same result with every tensor in host memory."""
-        return WindowResult(self.names, self.sequences, self.window, self.step, self.freqlimit, self.source, self.first_fit_rounds,
-                            self.windows.cpu(), *(getattr(self, k).cpu() for k in self._TENSORS))
 
     def _block(self, r):
         if not 0 <= r < len(self.names):
@@ -123,7 +112,7 @@ class WindowResult:
         eng = _engine.get_engine()
         if flat.is_cuda and hasattr(eng, "first_fit"):
             partner, info = eng.first_fit(flat, Ltot, 0)
-            _checked_status(info, None)
+            checked_fit(info, None)
         else:
             partner = torch.from_numpy(_first_fit_host(flat.cpu().numpy(), Ltot)).to(self.device)
         return _within_records(torch, partner, self.pos_off)
@@ -132,7 +121,7 @@ class WindowResult:
         """Sorted (i, j) pairs, i < j, of record r's consensus at the call's limit or at another one."""
         self._block(r)
         row = self.consensus if freqlimit is None else self.consensus_at(freqlimit)
-        return _row_pairs(row[int(self._pos_off[r]):int(self._pos_off[r + 1])].cpu().numpy())
+        return row_pairs(row[int(self._pos_off[r]):int(self._pos_off[r + 1])].cpu().numpy())
 
     def dbn(self, r, freqlimit=None, levellimit=None):
         """Dot-bracket line of record r's consensus (PairsToDBN; levellimit: cut to that many bracket levels)."""
@@ -154,14 +143,6 @@ class WindowResult:
         return band
 
 
-def _checked_status(info, rounds):
-    status, nrounds, npairs, live = info.tolist()
-    if status or live:
-        raise RuntimeError("sq_first_fit_dev: %d candidates still live after %d rounds" % (live, nrounds))
-    if rounds is not None:
-        rounds.append(nrounds)
-
-
 def _within_records(torch, partner, pos_off):
     """A partner row of the whole axis in the records' own coordinates."""
     lens = pos_off[1:] - pos_off[:-1]
@@ -172,16 +153,7 @@ def _within_records(torch, partner, pos_off):
 def _host_table(rows, gstart, wlens, wrec, rec_starts, pos_off, win_off, Ltot):
     """(flat, count, cover, first, rec) as numpy arrays from the consensus rows of a host FoldResult, unordered; first
     counts the windows of the whole call, as the kernel does."""
-    partner, cell_off = rows.partner.numpy(), rows._cell_off
-    keys, wins = [], []
-    for k in range(len(gstart)):
-        row = partner[cell_off[k]:cell_off[k] + wlens[k]]
-        t = np.flatnonzero(row > np.arange(len(row)))
-        keys.append((gstart[k] + t) * Ltot + gstart[k] + row[t])
-        wins.append(np.full(len(t), k, np.int64))
-    keys, wins = np.concatenate(keys), np.concatenate(wins)
-    flat, at, count = np.unique(keys, return_index=True, return_counts=True)
-    first = wins[at] if len(at) else np.zeros(0, np.int64)          # (the windows come in order: the first occurrence is the first holder)
+    flat, count, first = pair_table(rows.partner.numpy(), rows._cell_off, wlens, Ltot, gstart)
     rec = wrec[first] if len(first) else np.zeros(0, np.int64)
     cover = np.zeros(len(flat), np.int64)
     for r in np.unique(rec):                                         # the windows with start <= i and j < start + wlen: the starts ascend
@@ -208,12 +180,6 @@ def FoldWindows(inputfile=None, inputseq=None, records=None, window=150, step=No
     Windows across chain breaks or restraint pairs are not defined: a sequence with a gap or separator character and a
     restraint line that is not all '.' raise ValueError, as does ``bpp``.  A reference line is used for the metrics only."""
     import torch
-    pick = _fold._pick
-    kw = dict(fold_keywords)
-    inputfile = pick(inputfile, kw.pop("i", None)); inputseq = pick(inputseq, kw.pop("seq", None), kw.pop("s", None))
-    fileformat = pick(fileformat, kw.pop("ff", None)); ignorewarn = pick(ignorewarn, kw.pop("ignore", None), kw.pop("iw", None))
-    if kw.get("bpp") is not None:
-        raise ValueError("FoldWindows does not cover bpp: use Fold")
     try:
         ok = int(window) == window and int(window) >= 2
     except Exception:
@@ -230,24 +196,13 @@ def FoldWindows(inputfile=None, inputseq=None, records=None, window=150, step=No
     if not ok:
         raise ValueError("Inappropriate step value (integer between 1 and window): {}".format(step))
     step = int(step)
-    try:
-        freqlimit = float(freqlimit)
-        assert 0 <= freqlimit <= 1
-    except Exception:
-        raise ValueError("Inappropriate freqlimit value (float between 0.0 and 1.0): {}".format(freqlimit))
-    M, B = _fold._as_float(M, "M"), _fold._as_float(B, "B")
-    inputfile = _fold._check_sources(records, inputfile, inputseq, fileformat, kw.get("configfile"), inputformat,
-                                     kw.get("HOME_DIR"), kw.get("priority"))[0]
-    inputs = _fold._input_records(records, inputseq, inputfile, inputformat, fileformat, ignorewarn, kw.pop("inputrestr", None), M, B)
+    freqlimit = as_freqlimit(freqlimit)
+    inputs, kw = derived_inputs("FoldWindows", records, inputfile, inputseq, inputformat, fileformat, ignorewarn, M, B, fold_keywords)
 
     # ---- the windows
     names, seqs = [rec[0] for rec in inputs], [rec[1] for rec in inputs]
     R = len(inputs)
-    pos_off, win_off = np.zeros(R + 1, np.int64), np.zeros(R + 1, np.int64)
-    np.cumsum([len(s) for s in seqs], out=pos_off[1:])
-    Ltot = int(pos_off[-1])
-    if Ltot >= 2 ** 31:
-        raise ValueError("{} positions in all records: fewer than 2^31 are needed".format(Ltot))
+    (pos_off, Ltot), win_off = position_axis(seqs), np.zeros(R + 1, np.int64)
     wrecs, rec_starts = [], []
     for r, (name, seq, reacts, rests, _) in enumerate(inputs):
         if not seq or any(ch in GAPS or ch in SEPS for ch in seq):
@@ -270,7 +225,7 @@ def FoldWindows(inputfile=None, inputseq=None, records=None, window=150, step=No
     gstart = starts + pos_off[wrec]
     wlens = np.minimum(window, np.diff(pos_off))[wrec]
 
-    windows = _fold.Fold(records=wrecs, inputformat=inputformat, ignorewarn=ignorewarn, M=M, B=B, **kw)
+    windows = _fold.Fold(records=wrecs, **kw)
     assert windows._lengths.tolist() == wlens.tolist(), "a window's table does not have its length"
 
     eng = _engine.get_engine()
@@ -286,7 +241,7 @@ def FoldWindows(inputfile=None, inputseq=None, records=None, window=150, step=No
         order = _rank_order(torch, rec, freq, count, first, flat, T)
         flat, count, cover, first, rec, freq = (x[order] for x in (flat, count, cover, first, rec, freq))
         partner, info = eng.first_fit(flat[freq >= freqlimit], Ltot, 0)
-        _checked_status(info, rounds)
+        checked_fit(info, rounds)
     else:
         flat, count, cover, first, rec = _host_table(windows, gstart, wlens, wrec, rec_starts, pos_off, win_off, Ltot)
         freq = count.astype(np.float64) / cover.astype(np.float64)
@@ -306,7 +261,7 @@ def FoldWindows(inputfile=None, inputseq=None, records=None, window=150, step=No
         host = consensus.cpu().numpy()
         for r, rec5 in enumerate(inputs):
             if rec5[4]:
-                line = PairsToDBN(_row_pairs(host[pos_off[r]:pos_off[r + 1]]), len(seqs[r]))
+                line = PairsToDBN(row_pairs(host[pos_off[r]:pos_off[r + 1]]), len(seqs[r]))
                 metrics[r] = [float(x) for x in _align.Metrics(rec5[4], line)]
     return WindowResult(names, seqs, window, step, freqlimit, "device" if on_device else "host", rounds, windows, d_pos_off, d_win_off,
                         up(starts), pair_off, pair_pos, count.to(torch.int32), cover.to(torch.int32), pair_first, consensus, up(metrics))

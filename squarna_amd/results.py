@@ -1,10 +1,12 @@
 """Decoding of the library's packed result records (sq_result_pack layout, include/squarna_hip.h) and the containers of
 Predict's output blocks."""
+import copy
 import struct
 
 import numpy as np
 
 from .dbn import BRACKETS
+from .rows import offsets
 
 
 _HDR = struct.Struct("<4q")
@@ -18,6 +20,25 @@ _LEVEL_CP = np.full(2 * _NBR + 3, ord('.'), np.uint32)
 for _l in range(1, _NBR + 1):
     _LEVEL_CP[_NBR + 1 + _l] = ord(BRACKETS[_l - 1][0])
     _LEVEL_CP[_NBR + 1 - _l] = ord(BRACKETS[_l - 1][1])
+
+
+class TensorResult:
+    """What the result classes of the tensor entries share.  ``_TENSORS`` names a class's tensor attributes, ``_NESTED`` its
+    attributes that are results themselves (or None)."""
+    _TENSORS = ()
+    _NESTED = ()
+
+    @property
+    def device(self):
+        return getattr(self, self._TENSORS[0]).device
+
+    def cpu(self):
+        """The same result with every tensor in host memory."""
+        new = copy.copy(self)                                        # (host attributes and host caches: carried over as they are)
+        for k in self._TENSORS + self._NESTED:
+            if getattr(self, k) is not None:
+                setattr(new, k, getattr(self, k).cpu())
+        return new
 
 
 class _BlockRun:
@@ -135,8 +156,5 @@ def packed_pair_tables(buf, off):
         masks.append(np.frombuffer(raw, '<i8', ns, base + 160 + 24 * ns))
         partner.append(_level_partners(np.frombuffer(raw, '<i2', (ns + 1) * n, base + 160 + 32 * ns).reshape(ns + 1, n)).reshape(-1))
     cat = lambda parts, dt: np.concatenate(parts).astype(dt, copy=False) if parts else np.zeros(0, dt)
-    row_off, cell_off = np.zeros(nseq + 1, np.int64), np.zeros(nseq + 1, np.int64)
-    np.cumsum(nstruct, out=row_off[1:])
-    np.cumsum((1 + nstruct) * lengths, out=cell_off[1:])
     return dict(partner=cat(partner, np.int32), scores=cat(scores, np.float64).reshape(-1, 3), pset_mask=cat(masks, np.int64),
-                metrics=metrics, row_off=row_off, cell_off=cell_off), nstruct, lengths
+                metrics=metrics, row_off=offsets(nstruct), cell_off=offsets((1 + nstruct) * lengths)), nstruct, lengths

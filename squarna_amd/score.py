@@ -8,8 +8,6 @@ sequence, its stems, and TP FP FN FS PR RC against the record's known structure 
 are scored by a kernel (``sq_score_structs_dev``), one wave per row, and a tensor of partners that is on the device already
 is read where it is; an engine without ``score_tensors`` (the tests' CPU engine) gets the same object built on the CPU.
 """
-import contextlib
-import io
 import os
 
 import numpy as np
@@ -19,13 +17,12 @@ from .align import PairMetrics
 from .config import DATA_DIR
 from .core import ScoreStruct
 from .dbn import DBNToPairs, PairsToStems, ProcessReacts, ReactDict, SEPS, UnAlign, encode_seq, gap_mask
-from .inputs import ParseInput
+from .options import input_records
+from .results import TensorResult
+from .rows import offsets, partner_row
 
 #: the ranking tail's position limit (its LDS bitmap of paired positions)
 MAX_LENGTH = 32768
-
-_TENSORS = ("scores", "metrics", "status", "nstems", "npairs", "stems", "stem_off", "ref_scores", "row_off")
-
 
 class ScoreRecord:
     """One record of ``Score`` after the host's pre-processing, done once per record however many rows it has: the sequence
@@ -62,13 +59,12 @@ class ScoreRecord:
         else:
             self.reacts = None
         self.known = None
-        self.known_partner = np.full(self.n, -1, np.int32)
+        self.known_partner = partner_row((), self.n)
         if reference:
             if len(reference) != len(seq):
                 raise ValueError("Score: record {}: a known structure of {} columns for {}".format(name, len(reference), len(seq)))
             self.known = DBNToPairs(UnAlign(up, reference)[1])       # :965-967
-            for v, w in self.known:
-                self.known_partner[v], self.known_partner[w] = w, v
+            self.known_partner = partner_row(self.known, self.n)
 
     def score(self, pairs):
         """ScoreStruct of gap-free sorted pairs under this record, or None where the reference divides by zero."""
@@ -115,12 +111,11 @@ def _score_host(recs, partner, row_start, row_rec):
         if sc is not None:
             out["ref_scores"][r] = sc
     out["stems"] = np.array(stems, np.int32).reshape(-1, 3)
-    out["stem_off"] = np.zeros(rows + 1, np.int64)
-    np.cumsum(out["nstems"], out=out["stem_off"][1:])
+    out["stem_off"] = offsets(out["nstems"])
     return out
 
 
-class ScoreResult:
+class ScoreResult(TensorResult):
     """Scores of ``Score`` for the structure rows of R records.
 
     Host lists: ``names``, ``sequences`` (as given).  Torch tensors (``device``: where they live): ``row_off`` int64[R + 1]
@@ -132,21 +127,15 @@ class ScoreResult:
     one.  ``source``: "device" or "host" -- where the rows were scored.  ``recomputed``: how many rows and known structures the
     device handed back to the host (beyond the exact range of its rounding; 0 for every record below 32,768 nt)."""
 
+    _TENSORS = ("scores", "metrics", "status", "nstems", "npairs", "stems", "stem_off", "ref_scores", "row_off")
+
     def __init__(self, names, sequences, tables, source, recomputed=0):
         self.names, self.sequences, self.source, self.recomputed = names, sequences, source, recomputed
-        for k in _TENSORS:
+        for k in self._TENSORS:
             setattr(self, k, tables[k])
 
     def __len__(self):
         return len(self.names)
-
-    @property
-    def device(self):
-        return self.scores.device
-
-    def cpu(self):
-        """The same result with every tensor in host memory."""
-        return ScoreResult(self.names, self.sequences, {k: getattr(self, k).cpu() for k in _TENSORS}, self.source, self.recomputed)
 
     def stems_of(self, q):
         """[(i, j, len)] of row q."""
@@ -199,8 +188,7 @@ def _partner_rows(structures, nstruct, recs, on_device):
                     flat[at + v], flat[at + w] = w, v
                 at += int(lens[r])
         partner = torch.from_numpy(flat)
-    row_off = np.zeros(R + 1, np.int64)
-    np.cumsum(count, out=row_off[1:])
+    row_off = offsets(count)
     row_rec = np.repeat(np.arange(R, dtype=np.int32), count)
     k = np.arange(int(row_off[-1]), dtype=np.int64) - row_off[:-1][row_rec]
     row_start = np.asarray(first, np.int64)[row_rec] + k * stride[row_rec]
@@ -233,17 +221,12 @@ def Score(records=None, structures=None, inputfile=None, inputseq=None, inputfor
     from .fold import FoldResult
     if records is None and inputfile is None and not inputseq and isinstance(structures, FoldResult):
         records = [(name, seq, None, None, None) for name, seq in zip(structures.names, structures.sequences)]
-    if records is not None:
-        inputs = [(">record{}".format(k + 1), rec, None, None, None) if isinstance(rec, str) else tuple(rec)
-                  for k, rec in enumerate(records)]
-        assert all(len(rec) == 5 for rec in inputs), "records: sequences or (name, sequence, reactivities, restraints, reference)"
-    else:
+    if records is None:
         if inputfile is not None and not os.path.exists(inputfile) and os.path.exists(os.path.join(DATA_DIR, inputfile)):
             inputfile = os.path.join(DATA_DIR, inputfile)            # (as Fold: a name inside the package's data directory)
         assert inputseq or os.path.exists(str(inputfile)), "Input file does not exist."
-        with contextlib.redirect_stdout(io.StringIO()):              # (the parser announces a guessed file format)
-            inputs = list(ParseInput(inputseq, inputfile, inputformat, fmt=fileformat, ignore=ignorewarn, M=float(M), B=float(B))[0])
-    assert inputs, "No input records."
+        M, B = float(M), float(B)
+    inputs = input_records(records, inputseq, inputfile, inputformat, fileformat, ignorewarn, None, M, B)
     recs = [ScoreRecord(rec[0], rec[1], rec[2], rec[4]) for rec in inputs]
     if structures is None:
         structures = [[rec[4]] if rec[4] else [] for rec in inputs]

@@ -66,6 +66,8 @@ struct SqCoopSingle {
     SQ_HD void min_i32_at(int *p, int v) const { if (v < *p) *p = v; }
     SQ_HD void or_u32(uint32_t *p, uint32_t v) const { *p |= v; }
     SQ_HD int fetch_add_i32(int *p, int v) const { const int o = *p; *p += v; return o; }
+    SQ_HD unsigned long long min_u64(unsigned long long v) const { return v; }
+    SQ_HD int rank_true(bool p, int, int &total) const { total = p ? 1 : 0; return 0; }
 };
 #ifdef __HIPCC__
 // ... or the 64 lanes of a wave.  first_true: lowest lane whose predicate holds (nl if none);
@@ -81,6 +83,17 @@ struct SqCoopWave {
     __device__ void min_i32_at(int *p, int v) const { atomicMin(p, v); }
     __device__ void or_u32(uint32_t *p, uint32_t v) const { atomicOr(p, v); }
     __device__ int fetch_add_i32(int *p, int v) const { return atomicAdd(p, v); }
+    __device__ unsigned long long min_u64(unsigned long long v) const       // every lane gets the minimum over the lanes
+    {
+        for (int d = 32; d >= 1; d >>= 1) { const unsigned long long o = __shfl_xor(v, d, 64); v = o < v ? o : v; }
+        return v;
+    }
+    __device__ int rank_true(bool p, int lane, int &total) const          // lanes below this one whose predicate holds, and all of them
+    {
+        const unsigned long long b = __ballot(p);
+        total = (int)__popcll(b);
+        return (int)__popcll(b & ((1ull << lane) - 1ull));
+    }
     // *p = min(*p, v) for POSITIVE doubles (and +inf): their bit patterns order like unsigned integers
     __device__ void min_pos_f64(double *p, double v) const { atomicMin((unsigned long long *)p, (unsigned long long)__double_as_longlong(v)); }
     __device__ int first_true(bool p, int nl) const

@@ -17,6 +17,7 @@
 #include "sq_device.h"
 #include "sq_extend.h"
 #include "sq_tail_dev.h"
+#include "sq_choose.h"
 
 extern "C" __global__ __launch_bounds__(64) void sq_chain_kernel(SqDevCtx c, SqStruct *structs, SqScanArgs a, SqChainIO cio, int tmax)
 {
@@ -42,18 +43,11 @@ extern "C" __global__ __launch_bounds__(64) void sq_chain_kernel(SqDevCtx c, SqS
     };
     const unsigned long long ob = a.best[st.slot];
     if (ob == 0ull) { retire(ch.nstems, 0); return; }                   // no stem passed the thresholds: the structure is final
-    // ---- ChooseStems' first element: the highest finalscore, the smallest emission key among equals ----
-    const double bestfin = sq_unord(ob);
-    const uint32_t nok = a.ok_cnt[st.slot];
+    // ---- ChooseStems' first element (sq_choose.h) ----
     const SqOk *oks = sq_oks(a, st, jb.cand_cap);
-    unsigned long long pick = ~0ull;
-    for (uint32_t q = lane; q < nok; q += 64) {
-        const SqOk cd = oks[q];
-        if (cd.fin == bestfin) { const unsigned long long v = ((unsigned long long)cd.key << 32) | q; pick = v < pick ? v : pick; }
-    }
-    pick = sq_wave_min64(pick);
-    if (pick == ~0ull) { retire(ch.nstems, 0); return; }                // (not reachable: best comes from this list)
-    const SqOk cd = oks[(uint32_t)pick];
+    const uint32_t pick = sq_choose_first(SqChooseRecs<SqOk>{oks, a.ok_cnt[st.slot]}, sq_unord(ob), lane, 64, SqCoopWave());
+    if (pick == SQ_CHOOSE_NONE) { retire(ch.nstems, 0); return; }       // (not reachable: best comes from this list)
+    const SqOk cd = oks[pick];
     const int i0 = (int)(cd.key & 0xFFFFu), j0 = (int)(cd.key >> 16) - i0, len = (int)cd.len;
     const int k = ch.nstems;
     if (k >= ch.tcap) { if (lane == 0) a.ctr->out_ovf = 1; retire(k, 0); return; }

@@ -26,11 +26,6 @@ __device__ __forceinline__ unsigned long long sq_wave_or64(unsigned long long v)
     for (int d = 32; d >= 1; d >>= 1) v |= __shfl_xor(v, d, 64);
     return v;
 }
-__device__ __forceinline__ unsigned long long sq_wave_min64(unsigned long long v)
-{
-    for (int d = 32; d >= 1; d >>= 1) { const unsigned long long o = __shfl_xor(v, d, 64); v = o < v ? o : v; }
-    return v;
-}
 __device__ __forceinline__ int sq_wave_sum32(int v)
 {
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);

@@ -21,6 +21,7 @@
 #include "sq_cells.h"
 #include "sq_context.h"
 #include "sq_emit.h"
+#include "sq_state.h"
 
 // ------------------------------------------------------------------------------------
 // a-1  fill: one thread = 4 consecutive floats of the padded N x ld matrix (16-byte stores)
@@ -407,14 +408,7 @@ __device__ __forceinline__ void sq_state_build(const SqDevCtx &c, const SqStruct
     const uint8_t *codes = c.codes + jb.pos_off;
     for (int p = tid; p < n; p += nthr) { P[p] = -1; E[p] = e0[p]; }
     __syncthreads();
-    for (int k = tid; k < s.nstrand; k += nthr) {
-        const SqStrand x = sd[k];
-        for (int t = 0; t < x.len; t++) {
-            const int pos = x.start + t;
-            P[pos] = (int16_t)(x.pstart - t);           // :634-635
-            E[pos] = 255;                               // :446-451 row+column of a paired base are masked
-        }
-    }
+    sq_state_paint(P, E, sd, s.nstrand, tid, nthr);
     __syncthreads();
     // exclusive prefix counts of unpaired positions (U) and unpaired separators (SU): blockDim positions per step,
     // ballots inside a wave, the four wave totals through LDS, a running base across steps
@@ -434,20 +428,10 @@ __device__ __forceinline__ void sq_state_build(const SqDevCtx &c, const SqStruct
         __syncthreads();
     }
     if (tid == 0) { U[n] = (int16_t)base_u; SU[n] = (int16_t)base_s; }
-    // free-position bit words for the bit-diagonal scan: F bit p = (E[p] == 0); G bit k + SQ_GPAD = F[n-1-k].
-    // One ballot = two words.
+    // free-position bit words for the bit-diagonal scan, forward and reversed
     const int fbh = st.fbstride >> 1;
     uint32_t *FBs = st.FB + (int64_t)s.slot * st.fbstride;
-    for (int m2 = wv; 2 * m2 < fbh; m2 += nwv) {          // m2: pair of words (2 m2, 2 m2 + 1) of either array
-        const int pf = 64 * m2 + lane;                  // forward array: position
-        const unsigned long long bf = __ballot(pf < n && E[pf] == 0);
-        const int pr = n - 1 - (64 * m2 + lane - SQ_GPAD);   // reversed array: bit 64 m2 + lane <-> position n-1-(bit - pad)
-        const unsigned long long br = __ballot(pr >= 0 && pr < n && E[pr] == 0);
-        if (lane == 0) {
-            if (2 * m2 < fbh) { FBs[2 * m2] = (uint32_t)bf; FBs[fbh + 2 * m2] = (uint32_t)br; }
-            if (2 * m2 + 1 < fbh) { FBs[2 * m2 + 1] = (uint32_t)(bf >> 32); FBs[fbh + 2 * m2 + 1] = (uint32_t)(br >> 32); }
-        }
-    }
+    sq_free_words(E, n, fbh, FBs, lane, wv, nwv);
     if (LDS) {                                          // one coalesced write of everything
         __syncthreads();
         int16_t *gP = st.P + (int64_t)s.slot * st.stride, *gU = st.U + (int64_t)s.slot * st.stride;
@@ -683,22 +667,7 @@ __device__ __forceinline__ void sq_score_body(const SqDevCtx &c, const SqStruct 
 #else
     if (lds_strands && !use_ctx) {
 #endif
-        // Once the sweep of ScoreStems has registered the block [start, partner] of a 5' strand, the strands that
-        // start inside it are inert unless they are 5' strands whose partner lies beyond the block's end (they extend
-        // it or are wings); skip[k] = the first strand behind k that starts outside the block or is such a strand.
-        for (int k = tid; k < st.nstrand; k += nthr) {
-            const SqStrand x = s_str[k];
-            int q = k + 1;
-            if (x.left) {
-                const int pf = x.pstart;
-                while (q < st.nstrand) {
-                    const SqStrand y = s_str[q];
-                    if (y.start > pf || (y.left && y.pstart > pf)) break;
-                    q++;
-                }
-            }
-            s_skip[k] = (uint16_t)q;
-        }
+        sq_skip_pointers(s_str, st.nstrand, s_skip, tid, nthr);
     }
     const int16_t *P = stt.P + (int64_t)st.slot * stt.stride;
     const int16_t *U = stt.U + (int64_t)st.slot * stt.stride;

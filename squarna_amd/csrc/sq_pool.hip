@@ -6,9 +6,9 @@
 // the GPU -- bounded the throughput.  Here the structures of all pools live in device slots, two
 // generations of them (parents, children), and a round is
 //     state -> scan -> score -> sq_pool_choose_kernel -> sq_pool_scan_kernel -> sq_pool_extend_kernel
-//   choose   one wave per structure: the survivors within subopt x best (:769-778), ordered like the reference's stable
-//            descending sort (finalscore descending, emission key ascending), then the conflict filter (:779-789: a
-//            candidate joins when it shares a base with EVERY stem chosen so far) and the stopper (:1147);
+//   choose   one wave per structure: ChooseStems as sq_choose.h states it -- the survivors within subopt x best (:769-778)
+//            in the reference's order, the conflict filter (:779-789), or for a full pool the first element alone (:1147) --
+//            over the structure's SqOk records; the kernel adds the exits, the evaluation count and the flags;
 //   scan     one block: exclusive scan of the children counts = the children's slots (the next round's list keeps the
 //            reference's order: parents in order, each one's children in ChooseStems' order), per job the next list
 //            range, cursize / cursubopt (:1116-1120), the next round's size published to the host;
@@ -25,16 +25,9 @@
 #include "sq_device.h"
 #include "sq_extend.h"
 #include "sq_tail_dev.h"
+#include "sq_choose.h"
 
 #define SQ_POOL_NSURV 1024      // survivors within the range, per structure, the choose kernel sorts in LDS
-#define SQ_POOL_CMAX 64         // stems ChooseStems may return for one structure (== lanes of the conflict test)
-
-__device__ __forceinline__ bool sq_pool_shares_base(int ai, int aj, int al, int bi, int bj, int bl)   // :783-786
-{
-    const int as0 = ai, as1 = ai + al - 1, at0 = aj - al + 1, at1 = aj;
-    const int bs0 = bi, bs1 = bi + bl - 1, bt0 = bj - bl + 1, bt1 = bj;
-    return (as0 <= bs1 && bs0 <= as1) || (as0 <= bt1 && bt0 <= as1) || (at0 <= bs1 && bs0 <= at1) || (at0 <= bt1 && bt0 <= at1);
-}
 
 // start of a fold: the first generation (one empty structure per job), the job records and the header from pinned memory
 extern "C" __global__ __launch_bounds__(256) void sq_pool_init_kernel(const SqStruct *h_structs, const SqChain *h_recs,
@@ -81,72 +74,26 @@ extern "C" __global__ __launch_bounds__(64) void sq_pool_choose_kernel(SqDevCtx 
     const uint32_t nok = a.ok_cnt[st.slot];
     const SqOk *oks = sq_oks(a, st, jb.cand_cap);
     SqPoolPick *out = pio.chosen + (size_t)s * pio.cmax;
-    const bool one = J->cursize >= pio.poollim;             // :1147 stopper
-    if (one) {
-        // only ChooseStems' first element is used: the highest finalscore, the smallest emission key among equals
-        const double bestfin = sq_unord(ob);
-        unsigned long long pick = ~0ull;
-        for (uint32_t q = lane; q < nok; q += 64) {
-            const SqOk cd = oks[q];
-            if (cd.fin == bestfin) { const unsigned long long v = ((unsigned long long)cd.key << 32) | q; pick = v < pick ? v : pick; }
-        }
-        pick = sq_wave_min64(pick);
+    const SqChooseRecs<SqOk> src{oks, nok};
+    if (J->cursize >= pio.poollim) {                        // :1147 stopper: only ChooseStems' first element is used
+        const uint32_t pick = sq_choose_first(src, sq_unord(ob), lane, 64, SqCoopWave());
         if (lane == 0) {
-            if (pick == ~0ull) { pio.nchild[s] = 0; pio.finalflag[s] = 1; }
+            if (pick == SQ_CHOOSE_NONE) { pio.nchild[s] = 0; pio.finalflag[s] = 1; }
             else {
-                const SqOk cd = oks[(uint32_t)pick];
+                const SqOk cd = oks[pick];
                 out[0] = SqPoolPick{cd.key, cd.len, cd.bps, cd.fin};
                 pio.nchild[s] = 1; pio.finalflag[s] = 0;
             }
         }
         return;
     }
-    // ---- the candidates within range (:769-778) ----
-    const double range = J->cursubopt * sq_unord(ob);
-    int n = 0;
-    for (uint32_t q0 = 0; q0 < nok; q0 += 64) {
-        const uint32_t q = q0 + lane;
-        const bool valid = q < nok;
-        SqOk cd;
-        if (valid) cd = oks[q];
-        const bool keep = valid && !(cd.fin < range);
-        const unsigned long long m = __ballot(keep);
-        const int pos = n + __popcll(m & ((1ull << lane) - 1ull));
-        if (keep && pos < nsurv) { s_q[pos] = q; s_fin[pos] = cd.fin; s_key[pos] = cd.key; }
-        n += __popcll(m);
-    }
-    if (n > nsurv) {
-        if (lane == 0) { pio.hdr->ovf = 1; pio.nchild[s] = 0; pio.finalflag[s] = 0; }
-        return;
-    }
-    __syncthreads();
-    // ---- the reference's stable descending sort: finalscore descending, emission order (key) ascending ----
-    for (int x = lane; x < n; x += 64) {
-        const double fx = s_fin[x]; const uint32_t kx = s_key[x];
-        int r = 0;
-        for (int y = 0; y < n; y++) { const double fy = s_fin[y]; r += (fy > fx || (fy == fx && s_key[y] < kx)) ? 1 : 0; }
-        s_ord[r] = (uint16_t)x;
-    }
-    __syncthreads();
-    // ---- the conflict filter (:779-789): a candidate joins when it shares a base with every stem taken so far ----
-    int nres = 0;
-    bool over = false;
-    for (int t = 0; t < n; t++) {
-        const SqOk cd = oks[s_q[s_ord[t]]];
-        const int ci = (int)(cd.key & 0xFFFFu), cj = (int)(cd.key >> 16) - ci, cl = (int)cd.len;
-        const bool mine = lane < nres ? sq_pool_shares_base(ci, cj, cl, s_ri[lane], s_rj[lane], s_rl[lane]) : true;
-        if (__ballot(!mine) != 0ull) continue;
-        if (nres == SQ_POOL_CMAX || nres == pio.cmax) { over = true; break; }
-        if (lane == 0) {
-            s_ri[nres] = ci; s_rj[nres] = cj; s_rl[nres] = cl;
-            out[nres] = SqPoolPick{cd.key, cd.len, cd.bps, cd.fin};
-        }
-        nres++;
-        __syncthreads();
-    }
+    const SqChoice ch = sq_choose_stems(src, J->cursubopt * sq_unord(ob), nsurv, pio.cmax, s_fin, s_key, s_q, s_ord, s_ri, s_rj, s_rl,
+                                        lane, 64, [] { __syncthreads(); }, SqCoopWave(),
+                                        [&](int k, uint32_t key, int len, double bps, double fin) { out[k] = SqPoolPick{key, (uint32_t)len, bps, fin}; });
     if (lane == 0) {
-        if (over) { pio.hdr->ovf = 1; nres = 0; }
-        pio.nchild[s] = nres; pio.finalflag[s] = (nres == 0 && !over) ? 1 : 0;
+        const bool over = ch.taken < 0;                     // either overflow: the host repeats the fold with its own loop
+        if (over) pio.hdr->ovf = 1;
+        pio.nchild[s] = over ? 0 : ch.taken; pio.finalflag[s] = ch.taken == 0 ? 1 : 0;
     }
 }
 

@@ -7,13 +7,15 @@
 // short of exactly those slots.  Here ONE wave takes a structure through the whole of
 // OptimalStems (SQRNdbnseq.py:792-833) and ChooseStems (:754-789):
 //
-//   state       partner array, prefix counts, free-position words from the structure's sorted strands -- in LDS;
+//   state       partner array, prefix counts, free-position words from the structure's sorted strands -- in LDS, through
+//               the helpers the launched state kernel uses (sq_state.h);
 //   scan        AnnotateStems as the bit-diagonal scan (sq_scan.h); the runs are staged in LDS and, 64 at a time, given
 //               their exact bpscore at once (the candidate list never exists); those that pass :492 wait in LDS
 //               (beyond its room: in the structure's slice of the candidate arena);
 //   score       ScoreStems on them behind the bound of sq_cellrun.h, finalscores beside them in LDS;
-//   choose      the stopper's single pick (:1147), or the range :769-778, the reference's stable descending order and
-//               the conflict filter :779-789 -- sq_pool_choose_kernel's steps on LDS data.
+//   choose      ChooseStems as sq_choose.h states it -- the stopper's single pick (:1147), or the range :769-778, the
+//               reference's stable descending order and the conflict filter :779-789 -- with the survivors in LDS as its
+//               source and its arrays carved over the LDS the earlier phases are done with.
 //
 //   extend      comes FIRST: a child builds itself -- parent + its pick through sq_extend_structure (crossing weights, levels,
 //               sorted strands), strands straight into LDS -- and leaves its lists in its slot for its own children; the
@@ -38,14 +40,8 @@
 #include "sq_pool_round.h"
 #include "sq_rounds.h"             // (SqRun: a run with its exact bpscore -- the root lists' record)
 
-#define SQ_POOL_CMAX 64         // stems ChooseStems may return for one structure (== lanes of the conflict test)
-
-__device__ __forceinline__ bool sq_pr_shares_base(int ai, int aj, int al, int bi, int bj, int bl)   // :783-786
-{
-    const int as0 = ai, as1 = ai + al - 1, at0 = aj - al + 1, at1 = aj;
-    const int bs0 = bi, bs1 = bi + bl - 1, bt0 = bj - bl + 1, bt1 = bj;
-    return (as0 <= bs1 && bs0 <= as1) || (as0 <= bt1 && bt0 <= as1) || (at0 <= bs1 && bs0 <= at1) || (at0 <= bt1 && bt0 <= at1);
-}
+#include "sq_choose.h"
+#include "sq_state.h"
 
 // the survivors of :492: the first `cap` in LDS, the rest in the structure's slice of the candidate arena
 struct SqPrSurv {
@@ -74,6 +70,13 @@ struct SqPrSurv {
     }
     __device__ __forceinline__ void set_fin(uint32_t at, double f) { if (at < (uint32_t)cap) fin[at] = f; else spill[at - cap].fin = f; }
     __device__ __forceinline__ double get_fin(uint32_t at) const { return at < (uint32_t)cap ? fin[at] : spill[at - cap].fin; }
+};
+struct SqPrChooseSrc {              // the first `n` of them as ChooseStems' source (sq_choose.h)
+    const SqPrSurv &sv; uint32_t n;
+    __device__ __forceinline__ uint32_t size() const { return n; }
+    __device__ __forceinline__ double fin(uint32_t q) const { return sv.get_fin(q); }
+    __device__ __forceinline__ uint32_t key(uint32_t q) const { uint32_t k; int L; double b; sv.get(q, k, L, b); return k; }
+    __device__ __forceinline__ void get(uint32_t q, uint32_t &k, int &L, double &b) const { sv.get(q, k, L, b); }
 };
 
 // the scan's sink: runs staged in LDS; whenever 64 of them wait they get their bpscore and the ones that pass :492 join
@@ -372,14 +375,7 @@ __device__ __forceinline__ void sq_pool_round_body(const SqDevCtx &c, const SqSc
     {
         for (int p = lane; p < n; p += 64) { P[p] = -1; E[p] = ROOT ? c.e0c[jb.pos_off + p] : (uint8_t)(e4 >> (8 * (p >> 6))); }   // (c.e0c: asked for at the entry)
         __syncthreads();
-        for (int k = lane; k < st.nstrand; k += 64) {
-            const SqStrand x = s_str[k];
-            for (int t = 0; t < x.len; t++) {
-                const int pos = x.start + t;
-                P[pos] = (int16_t)(x.pstart - t);           // :634-635
-                E[pos] = 255;                               // :446-451 row + column of a paired base are masked
-            }
-        }
+        sq_state_paint(P, E, s_str, st.nstrand, lane, 64);
         __syncthreads();
         int base_u = 0, base_s = 0;
         for (int p0 = 0; p0 < n; p0 += 64) {
@@ -402,30 +398,8 @@ __device__ __forceinline__ void sq_pool_round_body(const SqDevCtx &c, const SqSc
             }
         }
         const int fbh = ROOT ? 0 : Lo.fbh;                   // (free-position words: the scan's)
-        for (int m2 = 0; 2 * m2 < fbh; m2++) {
-            const int pf = 64 * m2 + lane;
-            const unsigned long long bf = __ballot(pf < n && E[pf] == 0);
-            const int pr = n - 1 - (64 * m2 + lane - SQ_GPAD);
-            const unsigned long long br = __ballot(pr >= 0 && pr < n && E[pr] == 0);
-            if (lane == 0) {
-                FG[2 * m2] = (uint32_t)bf; FG[fbh + 2 * m2] = (uint32_t)br;
-                if (2 * m2 + 1 < fbh) { FG[2 * m2 + 1] = (uint32_t)(bf >> 32); FG[fbh + 2 * m2 + 1] = (uint32_t)(br >> 32); }
-            }
-        }
-        // skip pointers over the blocks ScoreStems' sweep registers (sq_score_kernel)
-        for (int k = lane; k < st.nstrand; k += 64) {
-            const SqStrand x = s_str[k];
-            int q = k + 1;
-            if (x.left) {
-                const int pf = x.pstart;
-                while (q < st.nstrand) {
-                    const SqStrand y = s_str[q];
-                    if (y.start > pf || (y.left && y.pstart > pf)) break;
-                    q++;
-                }
-            }
-            s_skip[k] = (uint16_t)q;
-        }
+        sq_free_words(E, n, fbh, FG, lane, 0, 1);
+        sq_skip_pointers(s_str, st.nstrand, s_skip, lane, 64);
         __syncthreads();
     }
 
@@ -758,19 +732,16 @@ __device__ __forceinline__ void sq_pool_round_body(const SqDevCtx &c, const SqSc
         return;
     }
 
-    // ---- ChooseStems (sq_pool_choose_kernel's steps) ----
+    // ---- ChooseStems (sq_choose.h) on the survivors ----
     SqPoolPick *out = pio.chosen + (cur + (size_t)s) * pio.cmax;
-    const bool one = cursize >= pio.poollim;             // :1147 stopper
-    if (one) {
-        // only ChooseStems' first element is used: the highest finalscore, the smallest emission key among equals
+    const SqPrChooseSrc src{sv, ns};
+    if (cursize >= pio.poollim) {                           // :1147 stopper: only ChooseStems' first element is used
+        // (sq_choose_first's loop written out: as a call it cost sq_pool_round_root_kernel, which runs at its register limit, two
+        // more spilled VGPRs.  best comes from this list: there is a pick)
         unsigned long long pick = ~0ull;
-        for (uint32_t q = lane; q < ns; q += 64)
-            if (sv.get_fin(q) == best) {
-                uint32_t key; int L; double bps;
-                sv.get(q, key, L, bps);
-                const unsigned long long v = ((unsigned long long)key << 32) | q; pick = v < pick ? v : pick;
-            }
-        pick = sq_wave_min64(pick);
+        for (uint32_t q = lane; q < src.size(); q += 64)
+            if (src.fin(q) == best) { const unsigned long long v = ((unsigned long long)src.key(q) << 32) | q; pick = v < pick ? v : pick; }
+        pick = SqCoopWave().min_u64(pick);
         if (lane == 0) {
             uint32_t key; int L; double bps;
             sv.get((uint32_t)pick, key, L, bps);
@@ -779,64 +750,29 @@ __device__ __forceinline__ void sq_pool_round_body(const SqDevCtx &c, const SqSc
         }
         return;
     }
-    // the candidates within range (:769-778), gathered over the arrays the earlier phases are done with
-    const double range = cursub * best;
-    double *const c_fin = reinterpret_cast<double *>(pr_dyn);
-    uint32_t *const c_key = reinterpret_cast<uint32_t *>(c_fin + Lo.choose_cap);
-    uint16_t *const c_q = reinterpret_cast<uint16_t *>(c_key + Lo.choose_cap), *const c_ord = c_q + Lo.choose_cap;
-    int nin = 0, nres = 0;
-    bool over_c = false;
-#ifdef SQ_PR_DUP_CHOOSE
-    for (int dup_ = 0; dup_ < 2; dup_++) { nin = 0; nres = 0; over_c = false; __syncthreads();
-#endif
-    for (uint32_t g = 0; g < ns; g += 64) {
-        const uint32_t q = g + lane;
-        const double f = q < ns ? sv.get_fin(q) : -INFINITY;
-        const bool keep = !(f < range);                     // (-inf: rejected or pruned)
-        uint32_t key = 0; int L = 0; double bps = 0.0;
-        if (keep) sv.get(q, key, L, bps);
-        const unsigned long long m = __ballot(keep);
-        const int pos = nin + __popcll(m & ((1ull << lane) - 1ull));
-        if (keep && pos < Lo.choose_cap) { c_q[pos] = (uint16_t)q; c_fin[pos] = f; c_key[pos] = key; }
-        nin += __popcll(m);
-    }
-    if (nin > Lo.choose_cap || ns > 65535u) {
+    if (ns > 65535u) {                                      // (the choose arrays index the survivors with 16 bits)
         if (lane == 0) { pio.hdr->ovf = 1; pio.nchild[s] = 0; pio.finalflag[s] = 0; }
         return;
     }
-    __syncthreads();
-    // the reference's stable descending sort: finalscore descending, emission order (key) ascending
-    for (int x = lane; x < nin; x += 64) {
-        const double fx = c_fin[x]; const uint32_t kx = c_key[x];
-        int r = 0;
-        for (int y = 0; y < nin; y++) { const double fy = c_fin[y]; r += (fy > fx || (fy == fx && c_key[y] < kx)) ? 1 : 0; }
-        c_ord[r] = (uint16_t)x;
-    }
-    __syncthreads();
-    // the conflict filter (:779-789): a candidate joins when it shares a base with every stem taken so far
-    for (int t = 0; t < nin; t++) {
-        const int x = c_ord[t];
-        uint32_t key; int cl; double bps;
-        sv.get(c_q[x], key, cl, bps);
-        const int ci = (int)(key & 0xFFFFu), cj = (int)(key >> 16) - ci;
-        const bool mine = lane < nres ? sq_pr_shares_base(ci, cj, cl, s_ri[lane], s_rj[lane], s_rl[lane]) : true;
-        if (__ballot(!mine) != 0ull) continue;
-        if (nres == SQ_POOL_CMAX || nres == pio.cmax) { over_c = true; break; }
-        if (lane == 0) {
-            s_ri[nres] = ci; s_rj[nres] = cj; s_rl[nres] = cl;
-            out[nres] = SqPoolPick{key, (uint32_t)cl, bps, c_fin[x]};
-        }
-        nres++;
-        __syncthreads();
-    }
+    // the arrays of the choice: over the ones the earlier phases are done with
+    double *const c_fin = reinterpret_cast<double *>(pr_dyn);
+    uint32_t *const c_key = reinterpret_cast<uint32_t *>(c_fin + Lo.choose_cap);
+    uint16_t *const c_q = reinterpret_cast<uint16_t *>(c_key + Lo.choose_cap), *const c_ord = c_q + Lo.choose_cap;
+    auto take = [&](int k, uint32_t key, int len, double bps, double fin) { out[k] = SqPoolPick{key, (uint32_t)len, bps, fin}; };
 #ifdef SQ_PR_DUP_CHOOSE
-    }
+    (void)sq_choose_stems(src, cursub * best, Lo.choose_cap, pio.cmax, c_fin, c_key, c_q, c_ord, s_ri, s_rj, s_rl, lane, 64, [] { __syncthreads(); }, SqCoopWave(), take);
+    __syncthreads();
 #endif
+    const SqChoice ch = sq_choose_stems(src, cursub * best, Lo.choose_cap, pio.cmax, c_fin, c_key, c_q, c_ord, s_ri, s_rj, s_rl,
+                                        lane, 64, [] { __syncthreads(); }, SqCoopWave(), take);
     PRPROF(5);
-    PRPROF_OUT(ns, nin);
-    if (over_c) { if (lane == 0) pio.hdr->ovf = 1; nres = 0; }
-    else if (nres == 0) log_final(2u * round + 1u, nstems);
-    if (lane == 0) { pio.nchild[s] = nres; pio.finalflag[s] = 0; }
+    PRPROF_OUT(ns, ch.in_range);
+    if (ch.taken < 0) {                                     // either overflow: the host repeats the fold with its own loop
+        if (lane == 0) { pio.hdr->ovf = 1; pio.nchild[s] = 0; pio.finalflag[s] = 0; }
+        return;
+    }
+    if (ch.taken == 0) log_final(2u * round + 1u, nstems);
+    if (lane == 0) { pio.nchild[s] = ch.taken; pio.finalflag[s] = 0; }
 }
 
 
@@ -910,16 +846,7 @@ extern "C" __global__ __launch_bounds__(64) void sq_pool_root_kernel(SqDevCtx c,
         const uint8_t *e0 = c.e0c + jb.pos_off;
         for (int p = lane; p < n; p += 64) E[p] = e0[p];
         __syncthreads();
-        for (int m2 = 0; 2 * m2 < fbh; m2++) {              // free-position words of the empty structure, forward and reversed
-            const int pf = 64 * m2 + lane;
-            const unsigned long long bf = __ballot(pf < n && E[pf] == 0);
-            const int pr = n - 1 - (64 * m2 + lane - SQ_GPAD);
-            const unsigned long long br = __ballot(pr >= 0 && pr < n && E[pr] == 0);
-            if (lane == 0) {
-                FG[2 * m2] = (uint32_t)bf; FG[fbh + 2 * m2] = (uint32_t)br;
-                if (2 * m2 + 1 < fbh) { FG[2 * m2 + 1] = (uint32_t)(bf >> 32); FG[fbh + 2 * m2 + 1] = (uint32_t)(br >> 32); }
-            }
-        }
+        sq_free_words(E, n, fbh, FG, lane, 0, 1);   // of the empty structure
         __syncthreads();
     }
     SqRun *const root = reinterpret_cast<SqRun *>(a.cands + ra.root_off + (int64_t)sx * ra.root_units);

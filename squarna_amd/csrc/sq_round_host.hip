@@ -1,5 +1,6 @@
 // sq_round_host.hip -- the launches of one round, the host-driven round driver, the per-call C ABI of a-1 .. a-6 (sq_bpmatrix_fill / _read, sq_optimal_stems) and alignment step 1.
 #include "sq_host_int.h"
+#include "sq_choose.h"
 
 // ---- a-1 -----------------------------------------------------------------------------------
 // full = 1: fp32 score matrices of every job (the API op).  full = 0: only what the fold path reads -- the
@@ -203,15 +204,6 @@ void sq_extend_struct(const HStruct &parent, const HStem &stem, HStruct &child, 
 }
 
 // ---- round driver ---------------------------------------------------------------------------
-static inline bool shares_base(const HStem &a, const HStem &b)       // SQRNdbnseq.py:783-786
-{
-    const int as0 = a.i, as1 = a.i + a.len - 1, at0 = a.j - a.len + 1, at1 = a.j;
-    const int bs0 = b.i, bs1 = b.i + b.len - 1, bt0 = b.j - b.len + 1, bt1 = b.j;
-    auto ov = [](int x0, int x1, int y0, int y1) { return x0 <= y1 && y0 <= x1; };
-    return ov(as0, as1, bs0, bs1) || ov(as0, as1, bt0, bt1) || ov(at0, at1, bs0, bs1) || ov(at0, at1, bt0, bt1);
-}
-
-
 // the kernels of one round over S structures: state arrays, bit-diagonal scan, exact scoring (mode 0: + ScoreStems),
 // and for host-driven greedy rounds the range filter that writes the round's output records
 void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64_t maxcap, bool need_reacts, double scan_bytes,
@@ -461,16 +453,14 @@ static int run_chunk(sq_batch *b, SqLane &ln, const std::vector<SView> &structs,
             for (uint32_t *p = p0; p < p1; p++) res.push_back(mk(*p));
             return;
         }
-        // ChooseStems (SQRNdbnseq.py:754-789): stable descending sort == (fin desc, emission key asc)
-        std::sort(p0, p1, [&](uint32_t x, uint32_t y) {
-            if (ho[x].fin != ho[y].fin) return ho[x].fin > ho[y].fin;
-            return ho[x].key < ho[y].key;
-        });
+        // ChooseStems (SQRNdbnseq.py:754-789) in sq_choose.h's order and with its conflict test; std::sort, not its rank sort: a
+        // big round's lists would make that quadratic
+        std::sort(p0, p1, [&](uint32_t x, uint32_t y) { return sq_choose_before(ho[y].fin, ho[y].key, ho[x].fin, ho[x].key); });
         res.push_back(mk(*p0));
         for (uint32_t *p = p0 + 1; p < p1; p++) {           // range filter already applied on device (:778)
             const HStem cand = mk(*p);
             bool all_conf = true;
-            for (const HStem &r : res) if (!shares_base(cand, r)) { all_conf = false; break; }
+            for (const HStem &r : res) if (!sq_shares_base(cand.i, cand.j, cand.len, r.i, r.j, r.len)) { all_conf = false; break; }
             if (all_conf) res.push_back(cand);
         }
     };

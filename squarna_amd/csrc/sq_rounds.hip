@@ -34,6 +34,8 @@
 #include "sq_score.h"
 #include "sq_scan.h"
 #include "sq_rounds.h"
+#include "sq_choose.h"
+#include "sq_state.h"
 
 #ifndef SQ_ROUNDS_WAVES
 #define SQ_ROUNDS_WAVES 4          // waves per SIMD the register budget allows (128 VGPRs): four 256-thread blocks per CU
@@ -236,16 +238,7 @@ extern "C" __global__ __launch_bounds__(SQ_ROUNDS_THREADS) __attribute__((amdgpu
     // ---- the first round's AnnotateStems: bit-diagonal scan of the empty structure into the staging half ----
     if (n >= 5) {                                                   // :456-457 (shorter sequences have no diagonals)
         const int fbh = Lo.fbh;
-        for (int m2 = wv; 2 * m2 < fbh; m2 += nwv) {                // free-position words, forward and reversed (sq_state_build)
-            const int pf = 64 * m2 + lane;
-            const unsigned long long bf = __ballot(pf < n && E[pf] == 0);
-            const int pr = n - 1 - (64 * m2 + lane - SQ_GPAD);
-            const unsigned long long br = __ballot(pr >= 0 && pr < n && E[pr] == 0);
-            if (lane == 0) {
-                FG[2 * m2] = (uint32_t)bf; FG[fbh + 2 * m2] = (uint32_t)br;
-                if (2 * m2 + 1 < fbh) { FG[2 * m2 + 1] = (uint32_t)(bf >> 32); FG[fbh + 2 * m2 + 1] = (uint32_t)(br >> 32); }
-            }
-        }
+        sq_free_words(E, n, fbh, FG, lane, wv, nwv);
         __syncthreads();
         SqRoundsSink sink{&s_nlist, raw, (uint32_t)cap, a.ctr};
         if (ra.fly > 0) {
@@ -764,7 +757,7 @@ extern "C" __global__ __launch_bounds__(SQ_ROUNDS_THREADS) __attribute__((amdgpu
         bany = 0; sfin = -INFINITY;
         for (int q = 0; q < nwv; q++) {
             if (s_wsec[q] > sfin) sfin = s_wsec[q];
-            if (s_wany[q] && (!bany || s_wfin[q] > bfin || (s_wfin[q] == bfin && s_wkey[q] < bkey))) {
+            if (s_wany[q] && (!bany || sq_choose_before(bfin, bkey, s_wfin[q], s_wkey[q]))) {
                 if (bany && bfin > sfin) sfin = bfin;
                 bany = 1; bfin = s_wfin[q]; bkey = s_wkey[q]; blen = s_wlen[q]; bbps = s_wbps[q];
             } else if (s_wany[q] && s_wfin[q] > sfin) sfin = s_wfin[q];
@@ -787,10 +780,7 @@ extern "C" __global__ __launch_bounds__(SQ_ROUNDS_THREADS) __attribute__((amdgpu
                 if (L == 0 || !(r.lf & SQ_RX_FIN) || r.key == bkey) continue;
                 if (LB[q].fin != bfin) continue;
                 const int i = (int)(r.key & 0xFFFFu), j = (int)(r.key >> 16) - i;
-                // strands [i, i + L) and (j - L, j] against the winner's
-                const bool hit = (i <= wi + wl - 1 && i + L - 1 >= wi) || (i <= wj && i + L - 1 >= wj - wl + 1) ||
-                                 (j - L + 1 <= wi + wl - 1 && j >= wi) || (j - L + 1 <= wj && j >= wj - wl + 1);
-                if (hit) found = 1;
+                if (sq_shares_base(i, j, L, wi, wj, wl)) found = 1;
             }
             if (__syncthreads_or(found)) {
                 if (tid == 0) {

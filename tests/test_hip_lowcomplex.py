@@ -172,6 +172,23 @@ def test_scan_form_round_kernel_equals_the_launched_round(config, cases, monkeyp
             b.close()
 
 
+@pytest.mark.parametrize("config,cases", [(k, sorted(v, key=lambda c: len(c["seq"]))[:2]) for k, v in _by_config(SHORT)],
+                         ids=[k for k, _ in _by_config(SHORT)])
+def test_host_loop_equals_the_launched_round(config, cases, monkeypatch):
+    """The host-driven loop (SQ_NO_POOL: driver 0) sorts and filters a round's records on the CPU, in sq_choose.h's order and
+    with its conflict test: on the two shortest records of a configuration, the packed record and the evaluation count of the
+    launched state / scan / score / choose kernels (SQ_NO_POOL_ROUND)."""
+    names, psets = conf(config)
+    for c in cases:
+        d, p, want, evals, _ = _fold_one(c, psets, dict(SQ_NO_POOL_ROUND="1"), monkeypatch)
+        assert d in (2, 3) and not (p & 8), (_case_id(c), d, p)
+        d, p, got, ev, res = _fold_one(c, psets, dict(SQ_NO_POOL="1"), monkeypatch)
+        assert d == 0, (_case_id(c), "driver", d, p)
+        check(res, c, _case_id(c))
+        assert got == want, _case_id(c)
+        assert ev == evals, _case_id(c)
+
+
 ONE = [c for c in CASES if c["kw"]["poollim"] == 1]
 
 

@@ -617,6 +617,52 @@ SQ_API size_t sq_score_scratch(int32_t nrec);
 SQ_API int sq_score_structs_dev(const sq_score_desc *d, const sq_score_rows *o, int32_t pass, void *d_scratch, size_t scratch_bytes,
                                 void *hip_stream);
 
+/* ---- loop and pseudoknot annotation of GIVEN structures (SQRNdbnseq.py:104-150 for the levels) ------------------------------
+ * sq_elements_rows -- for every partner row: the pseudoknot level of every pair (PairsToDBN's rule: pairs ordered by (crossing
+ * count, start), first-fitted into groups, the groups ranked by size, the largest is level 1), what every column is, and the
+ * loops that the pairs of level 1 close, with their sizes.  No sq_batch.  All pointers are the caller's DEVICE memory;
+ * everything is enqueued on hip_stream, nothing is allocated or waited for.
+ * Records (sq_elements_desc): d_pos_off, d_codes, d_col_off, d_colmap, d_gfcol as in sq_score_desc (the maps are NULL when no
+ * record has a gap column); max_len: the longest gap-free length of a record (<= 32768; sizes the LDS of the levels).
+ * Rows (sq_elements_rowset): row q is record d_row_rec[q]'s and starts at d_partner[d_row_start[q]], one int32 per INPUT column
+ * as for sq_score_rows; its per-column outputs start at d_cell_off[q] (int64[nrows + 1], the exclusive scan of the rows'
+ * widths; cells = its last entry): d_element int8 (0 exterior, 1 stem, 2 hairpin, 3 bulge, 4 internal, 5 multiloop, 6 a pair
+ * of level >= 2, 7 a separator, 8 a gap column; an unpaired column carries its loop's type), d_level int16 (+L opens, -L
+ * closes a pair of level L, else 0), d_loop_of int32 (the column's loop in the row's list; -1 for columns of kinds 1, 7, 8).
+ * Per row: d_status (0; 1 invalid: a partner outside the record, p[p[i]] != i, p[i] == i or a pair on a separator -- its
+ * columns hold -1, 0, -1 and it has no loop; 2: more stems than the LDS holds or more than 64 levels -- the caller annotates
+ * that row), d_npairs (after the pairs that touch a gap column are dropped), d_nlevels, d_nloops (0 unless the status is 0).
+ * d_loops [loop_cap][6] = (type, i, j, branches, unpaired, side5), i and j in input columns, row q's from d_loop_off[q] on:
+ * the exterior loop (-1, the row's width) first, then the loops by i ascending; stacks are not listed.
+ * pass 0 writes d_level, the kinds 1, 6, 7, 8 of d_element, d_status, d_npairs, d_nlevels, d_nloops; the caller forms d_loop_off
+ * int64[nrows + 1], the exclusive scan of d_nloops, and sizes d_loops; pass 1 writes the rest.  d_scratch:
+ * sq_elements_scratch(cells) bytes, the same memory for both passes (pass 0 leaves the loops' openers there).
+ * Returns 0, or -1 (bad argument, scratch too small: nothing enqueued). */
+typedef struct sq_elements_desc {
+    int32_t nrec, max_len;
+    const int64_t *d_pos_off;       /* [nrec + 1] */
+    const uint8_t *d_codes;
+    const int64_t *d_col_off;       /* [nrec + 1] or NULL */
+    const int32_t *d_colmap, *d_gfcol;
+} sq_elements_desc;
+typedef struct sq_elements_rowset {
+    int64_t nrows, cells;
+    const int32_t *d_partner;
+    const int64_t *d_row_start;     /* [nrows] */
+    const int32_t *d_row_rec;       /* [nrows] */
+    const int64_t *d_cell_off;      /* [nrows + 1] */
+    int8_t *d_element;              /* [cells] */
+    int16_t *d_level;               /* [cells] */
+    int32_t *d_loop_of;             /* [cells] */
+    int32_t *d_status, *d_npairs, *d_nlevels, *d_nloops;
+    const int64_t *d_loop_off;      /* [nrows + 1], pass 1 */
+    int32_t *d_loops;
+    int64_t loop_cap;
+} sq_elements_rowset;
+SQ_API size_t sq_elements_scratch(int64_t cells);
+SQ_API int sq_elements_rows(const sq_elements_desc *d, const sq_elements_rowset *o, int32_t pass, void *d_scratch, size_t scratch_bytes,
+                            void *hip_stream);
+
 /* ---- entropy mode as data (SQRNdbnseq.py:520-545, 1087-1089) ---------------------------------------------------------------
  * sq_entropy_rows -- for each listed job: AnnotateStems with no selected stem; its stems (len >= minlen, bpscore >= minbpscore)
  * form the symmetric N x N stem matrix, every cell (v, w) of a stem and its mirror holding the stem's total score; row i with

@@ -26,7 +26,7 @@ SYMBOLS = ["sq_version", "sq_last_error", "sq_last_capacity", "sq_batch_workspac
            "sq_host_cache_trim", "sq_align_first_fit", "sq_result_pairs_size", "sq_result_pairs_dev",
            "sq_align_pair_count_scratch", "sq_align_pair_count", "sq_first_fit_scratch", "sq_first_fit_dev",
            "sq_score_scratch", "sq_score_structs_dev", "sq_entropy_scratch", "sq_entropy_rows", "sq_window_pair_count",
-           "sq_variant_diff", "sq_duplex_summary", "sq_covariation_scratch", "sq_covariation_scan", "sq_covariation_pairs"]
+           "sq_variant_diff", "sq_duplex_summary", "sq_covariation_scratch", "sq_covariation_scan", "sq_covariation_pairs", "sq_elements_scratch", "sq_elements_rows"]
 
 BATCH_NO_FP32 = 1
 BATCH_POOL_LISTS = 2
@@ -98,6 +98,20 @@ class ScoreRows(C.Structure):
                 ("d_status", C.c_void_p), ("d_npairs", C.c_void_p), ("d_nstems", C.c_void_p), ("d_stem_off", C.c_void_p),
                 ("d_stems", C.c_void_p), ("stem_cap", C.c_int64), ("d_scores", C.c_void_p), ("d_metrics", C.c_void_p),
                 ("d_ref_scores", C.c_void_p), ("d_ref_status", C.c_void_p)]
+
+
+class ElementsDesc(C.Structure):
+    """sq_elements_desc: the records of sq_elements_rows (device pointers)."""
+    _fields_ = [("nrec", C.c_int32), ("max_len", C.c_int32), ("d_pos_off", C.c_void_p), ("d_codes", C.c_void_p),
+                ("d_col_off", C.c_void_p), ("d_colmap", C.c_void_p), ("d_gfcol", C.c_void_p)]
+
+
+class ElementsRows(C.Structure):
+    """sq_elements_rowset: the partner rows of sq_elements_rows and where their results go (device pointers)."""
+    _fields_ = [("nrows", C.c_int64), ("cells", C.c_int64), ("d_partner", C.c_void_p), ("d_row_start", C.c_void_p),
+                ("d_row_rec", C.c_void_p), ("d_cell_off", C.c_void_p), ("d_element", C.c_void_p), ("d_level", C.c_void_p),
+                ("d_loop_of", C.c_void_p), ("d_status", C.c_void_p), ("d_npairs", C.c_void_p), ("d_nlevels", C.c_void_p),
+                ("d_nloops", C.c_void_p), ("d_loop_off", C.c_void_p), ("d_loops", C.c_void_p), ("loop_cap", C.c_int64)]
 
 
 class FoldOpts(C.Structure):
@@ -204,6 +218,9 @@ def load():
     L.sq_score_scratch.restype = C.c_size_t
     L.sq_score_scratch.argtypes = [C.c_int32]
     L.sq_score_structs_dev.argtypes = [C.POINTER(ScoreDesc), C.POINTER(ScoreRows), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sq_elements_scratch.restype = C.c_size_t
+    L.sq_elements_scratch.argtypes = [C.c_int64]
+    L.sq_elements_rows.argtypes = [C.POINTER(ElementsDesc), C.POINTER(ElementsRows), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
     L.sq_entropy_scratch.restype = C.c_size_t
     L.sq_entropy_scratch.argtypes = [C.c_int32, C.c_int64]
     L.sq_entropy_rows.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -18,6 +18,12 @@ DUPLEX_SUMMARY_MAX_BLOCKS = 2048
 COVAR_TILE = 32
 COVAR_WORD_CHUNK = 4
 COVAR_MAX_BLOCKS = 2048
+#: the rows (waves) of a block of sq_elements_rows' loops kernel (SQ_ELEM_WAVES, csrc/sq_elements.h)
+ELEMENTS_WAVES = 4
+#: the stems and the pseudoknot levels of a row beyond which sq_elements_rows leaves it to the host (SQ_CHAIN_TMAX,
+#: csrc/sq_device.h; SQ_MAXLEVELS, csrc/sq_internal.h)
+ELEMENTS_MAX_STEMS = 11264
+ELEMENTS_MAX_LEVELS = 64
 
 
 def _ptr(t):
@@ -328,6 +334,57 @@ class DeviceCalls:
             o.d_stems, o.stem_cap = (_ptr(out["stems"]) if nstems else None), nstems
             _lib.check(L.sq_score_structs_dev(C.byref(d), C.byref(o), 1, _ptr(scratch), nbytes, stream))
         out["stem_off"] = stem_off
+        return out
+
+    def elements_tensors(self, recs, partner, row_start, row_rec):
+        """The loop and pseudoknot annotation of given structures on the device (sq_elements_rows).  recs, partner, row_start,
+        row_rec as for score_tensors.  Returns device tensors: element int8 / level int16 / loop_of int32 [cells] (row q's
+        columns from cell_off[q] on), cell_off int64[rows + 1], status / npairs / nlevels / nloops int32[rows], loop_off
+        int64[rows + 1], loops int32[S, 6].  A row of status 2 (more stems than the kernel's LDS holds, more than 64 levels) is
+        the caller's to annotate.  No sq_batch.  Enqueued on the current stream; the one wait is for the number of loops,
+        which sizes their tensor."""
+        import torch
+        assert partner.is_cuda and partner.dtype == torch.int32 and partner.dim() == 1 and partner.is_contiguous()
+        L = _lib.load()
+        dev, R, rows = partner.device, len(recs), len(row_rec)
+        pos_off = offsets([rec.n for rec in recs])
+        cat = lambda parts, dt: np.concatenate([np.asarray(p, dt).reshape(-1) for p in parts] + [np.zeros(0, dt)])
+        row_start, row_rec = np.asarray(row_start, np.int64).reshape(-1), np.asarray(row_rec, np.int32).reshape(-1)
+        width = np.array([len(rec.seq) for rec in recs], np.int64)[row_rec]
+        cell_off = offsets(width)
+        cells = int(cell_off[-1])
+        if rows:                                                     # (every row lies inside the tensor: the kernels trust it)
+            assert int(row_start.min()) >= 0 and int((row_start + width).max()) <= partner.numel(), "a row outside the partner tensor"
+        arrays = [pos_off, cell_off, row_start, row_rec, cat([rec.codes for rec in recs], np.uint8)]
+        gaps = any(rec.has_gap for rec in recs)
+        if gaps:                                                     # (the maps between input columns and gap-free positions)
+            arrays += [offsets([len(rec.colmap) for rec in recs]), cat([rec.colmap for rec in recs], np.int32),
+                       cat([rec.gfcol for rec in recs], np.int32)]
+        with torch.cuda.device(dev):
+            up = _upload_once([a if len(a) else np.zeros(1, a.dtype) for a in arrays], dev)
+            d = _lib.ElementsDesc(nrec=R, max_len=int(max((rec.n for rec in recs), default=0)), d_pos_off=_ptr(up[0]), d_codes=_ptr(up[4]))
+            if gaps:
+                d.d_col_off, d.d_colmap, d.d_gfcol = (_ptr(t) for t in up[5:8])
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            out = dict(element=new(cells, torch.int8), level=new(cells, torch.int16), loop_of=new(cells, torch.int32),
+                       status=new(rows, torch.int32), npairs=new(rows, torch.int32), nlevels=new(rows, torch.int32),
+                       nloops=new(rows, torch.int32))
+            nbytes = int(L.sq_elements_scratch(cells))
+            scratch = new(nbytes // 4, torch.int32)
+            loop_off = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
+            o = _lib.ElementsRows(nrows=rows, cells=cells, d_partner=_ptr(partner), d_row_start=_ptr(up[2]), d_row_rec=_ptr(up[3]),
+                                  d_cell_off=_ptr(up[1]), d_element=_ptr(out["element"]), d_level=_ptr(out["level"]),
+                                  d_loop_of=_ptr(out["loop_of"]), d_status=_ptr(out["status"]), d_npairs=_ptr(out["npairs"]),
+                                  d_nlevels=_ptr(out["nlevels"]), d_nloops=_ptr(out["nloops"]), d_loop_off=_ptr(loop_off), d_loops=None,
+                                  loop_cap=0)
+            stream = _stream(dev)
+            _lib.check(L.sq_elements_rows(C.byref(d), C.byref(o), 0, _ptr(scratch), nbytes, stream))
+            loop_off[1:] = torch.cumsum(out["nloops"], 0, dtype=torch.int64)
+            nloops = int(loop_off[-1].item())
+            out["loops"] = new((nloops, 6), torch.int32)
+            o.d_loops, o.loop_cap = (_ptr(out["loops"]) if nloops else None), nloops
+            _lib.check(L.sq_elements_rows(C.byref(d), C.byref(o), 1, _ptr(scratch), nbytes, stream))
+        out["loop_off"], out["cell_off"] = loop_off, up[1]
         return out
 
     def _pow17_table(self, nmax):

@@ -550,6 +550,31 @@ SQ_API int sq_covariation_scan(const uint8_t *d_rows, int32_t R, int32_t L, int3
 SQ_API int sq_covariation_pairs(const uint8_t *d_rows, int32_t R, int32_t L, const int32_t *d_pairs, int64_t P, void *d_scratch,
                                 size_t scratch_bytes, int32_t *d_counts, int64_t *d_cov, uint64_t *d_out, void *hip_stream);
 
+/* ---- the shuffled-column null of cov (CovariationSignificance) ---------------------------------------------------------
+ * Sample k of K permutes the rows of every column of the alignment on its own: row r of column c gets the key
+ * z = seed + 0x9E3779B97F4A7C15 * (1 + ((k * L + c) * R + r)) mod 2^64, the splitmix64 finaliser, (z & ~0xFFFF) | r, and row j
+ * of the shuffled column holds the class of the row with the j-th smallest key (csrc/sq_covar_null.h).  The in-scope cells
+ * of a sample are the v < w < L with w - v >= minspan; their covs are the null.
+ * sq_covariation_null: d_pairs int32[P * 2] and d_cov int64[P] are the observed pairs and their cov, d_thresholds int64[U]
+ * sorted distinct values (for CovariationSignificance those of d_cov).  Outputs: d_hist int64[U + 1], d_hist[b] = the null cells of all K samples with
+ * exactly b thresholds <= their cov; d_own_ge int32[P], the samples in which the cell of pair p has cov >= d_cov[p];
+ * d_null_max int64[K], the largest cov of a sample's cells (0 without a cell).  d_out[0] = 0, d_out[1] = 0, or 2 when a pair
+ * was not 0 <= v < w < L (it counts nothing).  The samples are formed `batch` at a time in d_scratch
+ * (sq_covariation_null_scratch(R, L, batch) bytes, 8-byte aligned: the bit planes of `batch` shuffled alignments and the
+ * class bytes of the rows); the results do not depend on batch.
+ * sq_covariation_null_planes: the planes of the samples k .. k + count - 1 alone, one after the other at the front of d_scratch
+ * (sq_covariation_null_scratch(R, L, count) bytes; layout of a sample's planes: csrc/sq_covar.h).
+ * Asynchronous on hip_stream, allocate nothing; 0, or -1 (a null pointer, R < 1, L < 1, K < 1, k < 0, batch or count outside 1..65535,
+ * a negative minspan, P or U, R above SQ_COVNULL_MAX_ROWS = 4096, L above 2^21, scratch too small: nothing enqueued;
+ * the pair pointers may be null when P is 0, d_thresholds when U is 0). */
+SQ_API size_t sq_covariation_null_scratch(int32_t R, int32_t L, int32_t batch);
+SQ_API int sq_covariation_null(const uint8_t *d_rows, int32_t R, int32_t L, int32_t minspan, const int32_t *d_pairs, const int64_t *d_cov,
+                               int64_t P, const int64_t *d_thresholds, int64_t U, int32_t K, uint64_t seed, int32_t batch, void *d_scratch,
+                               size_t scratch_bytes, int64_t *d_hist, int32_t *d_own_ge, int64_t *d_null_max, uint64_t *d_out,
+                               void *hip_stream);
+SQ_API int sq_covariation_null_planes(const uint8_t *d_rows, int32_t R, int32_t L, int64_t k, int32_t count, uint64_t seed,
+                                      void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
 /* ---- measurement ------------------------------------------------------------
  * Kernel ids: 0 fill, 1 state, 2 stem_scan, 3 stem_score (+ select), 4 Edmonds, 5 Hungarian,
  * 6 Nussinov, 9 the bpp terms formed at sq_batch_create from bpp_matrix_dev (both kernels; recorded whether profiling

@@ -48,14 +48,18 @@ def _cov_of(c):
     return sum(c[..., s] * c[..., t] * int(_D[s, t]) for s in range(6) for t in range(s + 1, 6))
 
 
-def _host_scan(rows, minspan, min_rows, min_cov):
-    """(pair_cols int32[P, 2] sorted by (v, w), counts int32[P, 7], cov int64[P]) with numpy: per pair type one int64 matrix
-    product of the two letters' one-hot matrices (deliberately not the kernel's bit-plane form)."""
-    cls = _classes(rows)
-    L = cls.shape[1]
+def _host_cells(cls):
+    """(c int64[L, L, 7], cov int64[L, L]) of every pair of columns of the class bytes cls uint8[R, L] with numpy: per pair type
+    one int64 matrix product of the two letters' one-hot matrices (deliberately not the kernel's bit-plane form)."""
     hot = [(cls == k).astype(np.int64) for k in range(5)]
     c = np.stack([hot["ACGU".index(t[0])].T @ hot["ACGU".index(t[1])] for t in TYPES] + [hot[4].T @ hot[4]], -1)
-    cov = _cov_of(c)
+    return c, _cov_of(c)
+
+
+def _host_scan(rows, minspan, min_rows, min_cov):
+    """(pair_cols int32[P, 2] sorted by (v, w), counts int32[P, 7], cov int64[P]) with numpy (_host_cells)."""
+    c, cov = _host_cells(_classes(rows))
+    L = rows.shape[1]
     v, w = np.indices((L, L))
     keep = (w > v) & (w - v >= minspan) & (c[..., :6].sum(-1) >= min_rows) & (cov >= min_cov)
     at = np.nonzero(keep)                                            # (row-major: sorted by (v, w))
@@ -162,7 +166,7 @@ def _read_alignment(inputfile, fileformat, inputformat, ignorewarn):
     return [obj[0] for obj in objs], [obj[1] for obj in objs]
 
 
-def _pair_list(pairs, alignment, L):
+def _pair_list(pairs, alignment, L, who="Covariation"):
     """None for a scan, else the pairs as an int32 array [P, 2] (or a torch tensor, taken as given)."""
     if pairs is None:
         pairs = "scan" if alignment is None else "steps"
@@ -171,44 +175,34 @@ def _pair_list(pairs, alignment, L):
             return None
         if pairs in ("steps", "table"):
             if alignment is None:
-                raise ValueError("Covariation: pairs={!r} needs alignment=".format(pairs))
+                raise ValueError("{}: pairs={!r} needs alignment=".format(who, pairs))
             if pairs == "table":
                 return alignment.pair_cols
             found = sorted(set(p for step in (1, 2, 3) for p in alignment.pairs(step)))
         elif len(pairs) == L:
             found = DBNToPairs(pairs)
         else:
-            raise ValueError("Covariation: pairs is 'scan', 'steps', 'table', a dot-bracket line of the alignment's {} columns, a list "
-                             "of (v, w) or an int tensor [P, 2]: {!r}".format(L, pairs))
+            raise ValueError("{}: pairs is 'scan', 'steps', 'table', a dot-bracket line of the alignment's {} columns, a list "
+                             "of (v, w) or an int tensor [P, 2]: {!r}".format(who, L, pairs))
         return np.array(found, np.int32).reshape(-1, 2)
     if hasattr(pairs, "dim"):                                        # a torch tensor
         if pairs.dim() != 2 or int(pairs.shape[1]) != 2 or pairs.is_floating_point():
-            raise ValueError("Covariation: a pairs tensor is an int tensor [P, 2]")
+            raise ValueError("{}: a pairs tensor is an int tensor [P, 2]".format(who))
         return pairs
     try:
         arr = np.array([tuple(p) for p in pairs]).reshape(-1, 2)
         assert arr.dtype.kind in "iu" or not arr.size
     except Exception:
-        raise ValueError("Covariation: pairs must be a list of (v, w) pairs of 0-based integers")
+        raise ValueError("{}: pairs must be a list of (v, w) pairs of 0-based integers".format(who))
     return arr.astype(np.int32)
 
 
-def Covariation(inputfile=None, fileformat="unknown", inputformat="qtrf", sequences=None, names=None, alignment=None, pairs=None,
-                minspan=4, min_rows=1, min_cov=1, ignorewarn=False):
-    """Covariation evidence for pairs of columns of an alignment, returned as a :class:`CovariationResult`.
-
-    Exactly one input: ``inputfile`` (parsed as ``FoldAlignment`` parses it), ``sequences`` (aligned strings, with ``names``
-    or numbered) or ``alignment`` (an :class:`AlignmentResult`: its sequences).  Rows are read upper-cased with T as U; a
-    byte is A, C, G, U, a gap (``- . ~``) or "other".
-
-    ``pairs``: None or "scan" -- every cell v < w with ``w - v >= minspan`` whose rows hold at least ``min_rows`` canonical
-    pairs and whose ``cov >= min_cov`` (the default without ``alignment``); "steps" -- the distinct pairs of the alignment's
-    three step lines, sorted (the default with ``alignment``); "table" -- the alignment's ``pair_cols``; a dot-bracket line
-    of L characters; a list of (v, w); an int tensor [P, 2].  Given pairs are taken as they are, in their order, whatever
-    the thresholds; one that is not 0 <= v < w < L raises RuntimeError."""
-    import torch
+def _open(who, inputfile, fileformat, inputformat, sequences, names, alignment, pairs, minspan, min_rows, min_cov, ignorewarn):
+    """The opening of Covariation and CovariationSignificance (`who` names the entry in messages): the input choice, the
+    thresholds and the pairs.  Returns (names, sequences, (minspan, min_rows, min_cov), the pairs as _pair_list gives them,
+    the rows as bytes uint8[R, L])."""
     if sum(x is not None for x in (inputfile, sequences, alignment)) != 1:
-        raise ValueError("Covariation: exactly one of inputfile, sequences and alignment is needed")
+        raise ValueError("{}: exactly one of inputfile, sequences and alignment is needed".format(who))
     if alignment is not None:
         names, seqs = list(alignment.names), list(alignment.sequences)
     elif inputfile is not None:
@@ -217,7 +211,7 @@ def Covariation(inputfile=None, fileformat="unknown", inputformat="qtrf", sequen
         seqs = [str(s) for s in sequences]
         names = list(names) if names is not None else [">record%d" % (k + 1) for k in range(len(seqs))]
         if len(names) != len(seqs):
-            raise ValueError("Covariation: {} names for {} sequences".format(len(names), len(seqs)))
+            raise ValueError("{}: {} names for {} sequences".format(who, len(names), len(seqs)))
     assert seqs and len(seqs[0]), "No input records."
     L = len(seqs[0])
     assert all(len(s) == L for s in seqs), 'The sequences are not aligned'
@@ -225,13 +219,24 @@ def Covariation(inputfile=None, fileformat="unknown", inputformat="qtrf", sequen
         minspan, min_rows, min_cov = int(minspan), int(min_rows), int(min_cov)
         assert min(minspan, min_rows, min_cov) >= 0
     except Exception:
-        raise ValueError("Covariation: minspan, min_rows and min_cov are non-negative integers")
-    given = _pair_list(pairs, alignment, L)
+        raise ValueError("{}: minspan, min_rows and min_cov are non-negative integers".format(who))
+    given = _pair_list(pairs, alignment, L, who)
     # one byte per character; a character beyond latin-1 is no base and no gap ('?')
     rows = np.frombuffer("".join(seqs).encode("latin-1", "replace"), np.uint8).reshape(len(seqs), L)
+    return names, seqs, (minspan, min_rows, min_cov), given, rows
 
-    eng = _engine.get_engine()
-    on_device = all(hasattr(eng, m) for m in _DEVICE_METHODS) and not hasattr(eng, "reduce_matrix")
+
+def _device_engine(eng, methods):
+    """Does the engine form the numbers on the device?  (The sharded engine and the tests' CPU engine do not.)"""
+    return all(hasattr(eng, m) for m in methods) and not hasattr(eng, "reduce_matrix")
+
+
+def _observe(who, eng, names, seqs, thresholds, given, rows, alignment):
+    """(CovariationResult, the rows on the result's device or None when it was formed on the host) of an opening."""
+    import torch
+    minspan, min_rows, min_cov = thresholds
+    L = rows.shape[1]
+    on_device, d_rows = _device_engine(eng, _DEVICE_METHODS), None
     if on_device:
         if alignment is not None and alignment.device.type == "cuda":
             dev = alignment.device
@@ -253,6 +258,25 @@ def Covariation(inputfile=None, fileformat="unknown", inputformat="qtrf", sequen
         cols = (given.cpu() if hasattr(given, "dim") else torch.from_numpy(given)).to(torch.int32).contiguous()
         p = cols.numpy()
         if len(p) and not ((p[:, 0] >= 0) & (p[:, 0] < p[:, 1]) & (p[:, 1] < L)).all():
-            raise RuntimeError("Covariation: a pair is not 0 <= v < w < %d columns" % L)
+            raise RuntimeError("%s: a pair is not 0 <= v < w < %d columns" % (who, L))
         counts, cov = (torch.from_numpy(a) for a in _host_pairs(rows, p))
-    return CovariationResult(names, seqs, "scan" if given is None else "pairs", "device" if on_device else "host", cols, counts, cov)
+    res = CovariationResult(names, seqs, "scan" if given is None else "pairs", "device" if on_device else "host", cols, counts, cov)
+    return res, d_rows
+
+
+def Covariation(inputfile=None, fileformat="unknown", inputformat="qtrf", sequences=None, names=None, alignment=None, pairs=None,
+                minspan=4, min_rows=1, min_cov=1, ignorewarn=False):
+    """Covariation evidence for pairs of columns of an alignment, returned as a :class:`CovariationResult`.
+
+    Exactly one input: ``inputfile`` (parsed as ``FoldAlignment`` parses it), ``sequences`` (aligned strings, with ``names``
+    or numbered) or ``alignment`` (an :class:`AlignmentResult`: its sequences).  Rows are read upper-cased with T as U; a
+    byte is A, C, G, U, a gap (``- . ~``) or "other".
+
+    ``pairs``: None or "scan" -- every cell v < w with ``w - v >= minspan`` whose rows hold at least ``min_rows`` canonical
+    pairs and whose ``cov >= min_cov`` (the default without ``alignment``); "steps" -- the distinct pairs of the alignment's
+    three step lines, sorted (the default with ``alignment``); "table" -- the alignment's ``pair_cols``; a dot-bracket line
+    of L characters; a list of (v, w); an int tensor [P, 2].  Given pairs are taken as they are, in their order, whatever
+    the thresholds; one that is not 0 <= v < w < L raises RuntimeError."""
+    names, seqs, thresholds, given, rows = _open("Covariation", inputfile, fileformat, inputformat, sequences, names, alignment, pairs,
+                                                 minspan, min_rows, min_cov, ignorewarn)
+    return _observe("Covariation", _engine.get_engine(), names, seqs, thresholds, given, rows, alignment)[0]

@@ -18,6 +18,13 @@ DUPLEX_SUMMARY_MAX_BLOCKS = 2048
 COVAR_TILE = 32
 COVAR_WORD_CHUNK = 4
 COVAR_MAX_BLOCKS = 2048
+#: the most rows sq_covariation_null shuffles on the device and the bins its scan keeps in LDS (SQ_COVNULL_MAX_ROWS,
+#: SQ_COVNULL_LDS_BINS, csrc/sq_covar_null.h)
+COVAR_NULL_MAX_ROWS = 4096
+COVAR_NULL_LDS_BINS = 4096
+#: the bytes of shuffled planes covariation_null keeps at a time unless told a batch, and the most samples of a batch
+COVAR_NULL_BATCH_BYTES = 256 << 20
+COVAR_NULL_BATCH = 64
 #: the rows (waves) of a block of sq_elements_rows' loops kernel (SQ_ELEM_WAVES, csrc/sq_elements.h)
 ELEMENTS_WAVES = 4
 #: the stems and the pseudoknot levels of a row beyond which sq_elements_rows leaves it to the host (SQ_CHAIN_TMAX,
@@ -277,6 +284,60 @@ class DeviceCalls:
                                               _ptr(counts if P else None), _ptr(cov if P else None), _ptr(out), _stream(dev)))
             _result_words(out, "sq_covariation_pairs: a pair is not 0 <= v < w < %d columns" % Lcols)
         return counts, cov
+
+    def covariation_null_planes(self, rows, k, seed, count=None):
+        """The bit planes of sample k of the shuffled-column null of an alignment (sq_covariation_null_planes): rows = uint8
+        device tensor [R, L]; returns the int64 device tensor [5, ceil(R / 64), L rounded up to 64] of the planes A, C, G, U, gap
+        (csrc/sq_covar.h has the layout, csrc/sq_covar_null.h the shuffle).  With `count`: the samples k .. k + count - 1 from one
+        launch, as [count, 5, ceil(R / 64), L rounded up to 64]."""
+        import torch
+        L = _lib.load()
+        assert rows.dtype == torch.uint8 and rows.is_cuda and rows.dim() == 2 and rows.is_contiguous()
+        dev, R, Lcols, many = rows.device, int(rows.shape[0]), int(rows.shape[1]), 1 if count is None else int(count)
+        words, lpad = (R + 63) // 64, (Lcols + 63) // 64 * 64
+        with torch.cuda.device(dev):
+            nbytes = int(L.sq_covariation_null_scratch(R, Lcols, many))
+            scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+            _lib.check(L.sq_covariation_null_planes(_ptr(rows), R, Lcols, int(k), many, int(seed), _ptr(scratch), nbytes, _stream(dev)))
+        planes = scratch[:many * 5 * words * lpad].view(many, 5, words, lpad)
+        return planes[0] if count is None else planes
+
+    def covariation_null(self, rows, pairs, cov, minspan=4, samples=100, seed=0, batch=None):
+        """The shuffled-column null of cov for observed pairs (sq_covariation_null): rows = uint8 device tensor [R, L], pairs =
+        int32 device tensor [P, 2], cov = int64 device tensor [P] (their observed values).  Returns the device tensors
+        (null_ge int64[P] = the null cells of all samples with cov >= cov[p], own_ge int32[P] = the samples in which the same
+        cell reaches cov[p], null_max int64[samples]).  `batch` samples are formed at a time (default: as many as
+        COVAR_NULL_BATCH_BYTES of planes hold, at most COVAR_NULL_BATCH); the results do not depend on it.  RuntimeError when a
+        pair is not 0 <= v < w < L.  Only the two result words come to the host."""
+        import torch
+        L = _lib.load()
+        assert rows.dtype == torch.uint8 and rows.is_cuda and rows.dim() == 2 and rows.is_contiguous()
+        assert pairs.dtype == torch.int32 and pairs.dim() == 2 and int(pairs.shape[1]) == 2 and pairs.device == rows.device
+        assert cov.dtype == torch.int64 and cov.dim() == 1 and cov.device == rows.device and int(cov.numel()) == int(pairs.shape[0])
+        dev, R, Lcols, P, K = rows.device, int(rows.shape[0]), int(rows.shape[1]), int(pairs.shape[0]), int(samples)
+        pairs, cov = pairs.contiguous(), cov.contiguous()
+        if batch is None:
+            per = 5 * ((R + 63) // 64) * ((Lcols + 63) // 64 * 64) * 8
+            batch = max(1, min(K, COVAR_NULL_BATCH, COVAR_NULL_BATCH_BYTES // per))
+        batch = int(batch)
+        with torch.cuda.device(dev):
+            thresholds = torch.unique(cov)                           # (sorted)
+            U = int(thresholds.numel())
+            nbytes = int(L.sq_covariation_null_scratch(R, Lcols, batch))
+            scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+            hist = torch.empty(U + 1, dtype=torch.int64, device=dev)
+            own_ge = torch.empty(P, dtype=torch.int32, device=dev)
+            null_max = torch.empty(K, dtype=torch.int64, device=dev)
+            out = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.check(L.sq_covariation_null(_ptr(rows), R, Lcols, int(minspan), _ptr(pairs if P else None), _ptr(cov if P else None), P,
+                                             _ptr(thresholds if U else None), U, K, int(seed), batch, _ptr(scratch), nbytes, _ptr(hist),
+                                             _ptr(own_ge if P else None), _ptr(null_max), _ptr(out), _stream(dev)))
+            _result_words(out, "sq_covariation_null: a pair is not 0 <= v < w < %d columns" % Lcols)
+            # hist[b] = the null cells with exactly b thresholds <= their cov: cov[p], the t-th threshold, is reached by the bins
+            # from t + 1 on
+            from_bin = torch.flip(torch.cumsum(torch.flip(hist, (0,)), 0), (0,))
+            null_ge = from_bin[torch.searchsorted(thresholds, cov) + 1] if P else torch.empty(0, dtype=torch.int64, device=dev)
+        return null_ge, own_ge, null_max
 
     def score_tensors(self, recs, partner, row_start, row_rec):
         """ScoreStruct, stems and metrics of given structures on the device (sq_score_structs_dev; SQRNdbnseq.py:958-970,

@@ -575,6 +575,31 @@ SQ_API int sq_covariation_null(const uint8_t *d_rows, int32_t R, int32_t L, int3
 SQ_API int sq_covariation_null_planes(const uint8_t *d_rows, int32_t R, int32_t L, int64_t k, int32_t count, uint64_t seed,
                                       void *d_scratch, size_t scratch_bytes, void *hip_stream);
 
+/* ---- row identities, neighbour counts and the redundancy filter of an alignment (RowIdentity) ----------------------------
+ * d_rows uint8[R * L] as for the covariation entries, the bytes classified in the same way; a residue is any non-gap, a base
+ * is A, C, G or U, and "other" matches nothing.  For rows a, b: same[a, b] = the columns where both hold the same base,
+ * both[a, b] = the columns where both hold a residue, len[a] = both[a, a], bases[a] = same[a, a].  The denominator den(a, b)
+ * is min(len[a], len[b]) (denominator 0, "shorter"), both[a, b] (1, "aligned") or L (2, "columns"); rows a != b are neighbours
+ * iff den > 0 and same * 10000 >= threshold_bp * den, in int64.  Outputs: d_len, d_bases, d_neighbours int32[R]
+ * (neighbours[a] = 1 + the neighbours of a), d_keep uint8[R] (the greedy filter in row order: row a is kept iff no kept row
+ * b < a is its neighbour), and d_same, d_both int32[R * R] (symmetric, the diagonal included), which may both be null: then no
+ * matrix is written.  d_out[0] = d_out[1] = 0.  d_scratch (sq_row_identity_scratch(R, L) bytes, 8-byte aligned; 0 for sizes
+ * the entry refuses) holds the rows as four bit planes of 64 columns per word and the neighbour bit matrix
+ * uint64[R * ceil(R / 64)] (csrc/sq_identity.h has both layouts).  Three kernels, one after the other: the planes, all pairs
+ * of rows in tiles of 64 x 64 from LDS, the filter as one wave.
+ * Asynchronous on hip_stream, allocates nothing; 0, or -1 (a null pointer other than the two matrices, exactly one of the
+ * two matrices, R < 1, L < 1, R above SQ_ID_MAX_ROWS = 65535, L above 2^21, a denominator outside 0..2, threshold_bp outside
+ * 0..10000, scratch too small: nothing enqueued, nothing written).
+ * sq_row_identity_phases: the same call with only the kernels of `phases` (bit 0: the planes with len and bases, bit 1: all
+ * pairs, bit 2: the filter; 1..7, else -1) on buffers that hold what the earlier phases left: for measuring a kernel alone. */
+SQ_API size_t sq_row_identity_scratch(int32_t R, int32_t L);
+SQ_API int sq_row_identity(const uint8_t *d_rows, int32_t R, int32_t L, int32_t denominator, int32_t threshold_bp, void *d_scratch,
+                           size_t scratch_bytes, int32_t *d_len, int32_t *d_bases, int32_t *d_same, int32_t *d_both,
+                           int32_t *d_neighbours, uint8_t *d_keep, uint64_t *d_out, void *hip_stream);
+SQ_API int sq_row_identity_phases(int32_t phases, const uint8_t *d_rows, int32_t R, int32_t L, int32_t denominator, int32_t threshold_bp,
+                                  void *d_scratch, size_t scratch_bytes, int32_t *d_len, int32_t *d_bases, int32_t *d_same,
+                                  int32_t *d_both, int32_t *d_neighbours, uint8_t *d_keep, uint64_t *d_out, void *hip_stream);
+
 /* ---- measurement ------------------------------------------------------------
  * Kernel ids: 0 fill, 1 state, 2 stem_scan, 3 stem_score (+ select), 4 Edmonds, 5 Hungarian,
  * 6 Nussinov, 9 the bpp terms formed at sq_batch_create from bpp_matrix_dev (both kernels; recorded whether profiling

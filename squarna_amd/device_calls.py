@@ -25,6 +25,17 @@ COVAR_NULL_LDS_BINS = 4096
 #: the bytes of shuffled planes covariation_null keeps at a time unless told a batch, and the most samples of a batch
 COVAR_NULL_BATCH_BYTES = 256 << 20
 COVAR_NULL_BATCH = 64
+#: sq_row_identity's tile of rows, the 64-column words it keeps in LDS at a time, the most blocks it launches, the most rows
+#: and columns it takes and the words of neighbour bits a lane of its filter kernel holds ahead (SQ_ID_TILE, SQ_ID_WORD_CHUNK, SQ_ID_MAX_BLOCKS,
+#: SQ_ID_MAX_ROWS, SQ_ID_MAX_COLS, SQ_ID_FILTER_WORDS, csrc/sq_identity.h)
+IDENTITY_TILE = 64
+IDENTITY_WORD_CHUNK = 4
+IDENTITY_MAX_BLOCKS = 2048
+IDENTITY_MAX_ROWS = 65535
+IDENTITY_MAX_COLS = 1 << 21
+IDENTITY_FILTER_WORDS = 64
+#: the denominators of sq_row_identity by name (SQ_ID_DEN_*, csrc/sq_identity.h)
+IDENTITY_DENOMINATORS = ("shorter", "aligned", "columns")
 #: the rows (waves) of a block of sq_elements_rows' loops kernel (SQ_ELEM_WAVES, csrc/sq_elements.h)
 ELEMENTS_WAVES = 4
 #: the stems and the pseudoknot levels of a row beyond which sq_elements_rows leaves it to the host (SQ_CHAIN_TMAX,
@@ -338,6 +349,30 @@ class DeviceCalls:
             from_bin = torch.flip(torch.cumsum(torch.flip(hist, (0,)), 0), (0,))
             null_ge = from_bin[torch.searchsorted(thresholds, cov) + 1] if P else torch.empty(0, dtype=torch.int64, device=dev)
         return null_ge, own_ge, null_max
+
+    def row_identity(self, rows, denominator=0, threshold_bp=8000, matrix=True):
+        """Row identities, neighbour counts and the greedy redundancy filter of an alignment, on the device (sq_row_identity):
+        rows = uint8 device tensor [R, L] of the rows' ASCII bytes, denominator = 0 / 1 / 2 (IDENTITY_DENOMINATORS: the
+        shorter row's residues, the columns where both hold a residue, L), threshold_bp = the neighbour threshold in basis
+        points.  Returns a dict of device tensors: len, bases, neighbours int32[R], keep bool[R] and, with `matrix`, same and
+        both int32[R, R] (else None: then nothing of size R x R is written).  Only the two result words come to the host."""
+        import torch
+        L = _lib.load()
+        assert rows.dtype == torch.uint8 and rows.is_cuda and rows.dim() == 2 and rows.is_contiguous()
+        dev, R, Lcols = rows.device, int(rows.shape[0]), int(rows.shape[1])
+        with torch.cuda.device(dev):
+            nbytes = int(L.sq_row_identity_scratch(R, Lcols))
+            scratch = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            res = dict(len=new(R, torch.int32), bases=new(R, torch.int32), neighbours=new(R, torch.int32), keep=new(R, torch.uint8),
+                       same=new((R, R), torch.int32) if matrix else None, both=new((R, R), torch.int32) if matrix else None)
+            out = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.check(L.sq_row_identity(_ptr(rows), R, Lcols, int(denominator), int(threshold_bp), _ptr(scratch), nbytes, _ptr(res["len"]),
+                                         _ptr(res["bases"]), _ptr(res["same"]), _ptr(res["both"]), _ptr(res["neighbours"]),
+                                         _ptr(res["keep"]), _ptr(out), _stream(dev)))
+            _result_words(out, "sq_row_identity: status")            # (the entry has no status: out[1] stays 0)
+        res["keep"] = res["keep"].bool()
+        return res
 
     def score_tensors(self, recs, partner, row_start, row_rec):
         """ScoreStruct, stems and metrics of given structures on the device (sq_score_structs_dev; SQRNdbnseq.py:958-970,

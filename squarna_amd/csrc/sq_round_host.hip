@@ -8,12 +8,13 @@
 // through the fp32 fill (it imports the bool matrix and forms score * multiplier in the dense arena).
 int sq_fill_impl(sq_batch *b, int full)
 {
-    int64_t maxq = 0, maxw = 0; double bytes = 0; bool any_ext1 = false, any_ext = false;
+    int64_t maxq = 0, maxw = 0; double bytes = 0; bool any_ext1 = false, any_ext = false; int maxlds = 0;
     for (const SqJob &J : b->jobs) {
         maxq = std::max<int64_t>(maxq, ((int64_t)J.n * J.ld + 3) / 4);
         maxw = std::max<int64_t>(maxw, (int64_t)J.nw * ((J.bpitch + 255) / 256));
         if (full || J.has_ext) bytes += 4.0 * J.n * J.n;                // algorithmic: one fp32 N x N write
         any_ext1 |= J.has_ext == 1; any_ext |= J.has_ext != 0;
+        if (J.n <= 4096) maxlds = std::max(maxlds, (int)J.n);       // (SQ_FILL_LDS_N: the longest job the fill may stage in LDS)
     }
     for (int j0 = 0; j0 < b->njobs; j0 += 32768) {
         const int nj = std::min(32768, b->njobs - j0);
@@ -28,7 +29,9 @@ int sq_fill_impl(sq_batch *b, int full)
             const int fper_env = sq_tuning().fill_per;
             const int64_t fper = 256 * (fper_env > 0 ? (int64_t)fper_env
                                                      : std::min<int64_t>(std::max<int64_t>(maxq * nj / (256 * 4096), 4), 64));
-            const size_t fdyn = lds_inputs ? (size_t)12 * ((b->maxn + 15) & ~15) + 64 : 0;
+            // (the kernel picks its path per JOB: a batch whose longest sequence is beyond SQ_FILL_LDS_N still stages its shorter
+            // jobs in LDS, so the room is that of the longest job that may take the path, not 0)
+            const size_t fdyn = maxlds ? (size_t)12 * ((maxlds + 15) & ~15) + 64 : 0;
             dim3 fgrid(lds_inputs ? (unsigned)std::min<int64_t>(std::max<int64_t>((maxq + fper - 1) / fper, 1), 1024) : grid.x, (unsigned)nj);
             hipLaunchKernelGGL(sq_fill_kernel, fgrid, dim3(256), fdyn, b->stream, c, full ? 0 : 1, b->mul_applied ? 1 : 0);
         }

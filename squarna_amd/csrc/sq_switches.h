@@ -52,7 +52,8 @@ struct SqBatchSwitches {
     double kept_gb = 48.0;            // SQ_KEPT_GB: upper limit of the kept lists' pages in all (at least 0.01)
     int fin_stem_cap = 0;             // SQ_FIN_STEM_CAP: caps the stem room of the log of final structures (0: none; else at least 16)
     bool no_shared_bits = false;      // SQ_NO_SHARED_BITS: every job gets its own diagonal bit matrix
-    bool bits_direct = false;         // SQ_BITS_DIRECT: sq_bpmatrix_fill derives the bit matrices from the O(N) inputs
+    bool bits_direct = false;         // SQ_BITS_DIRECT: sq_bpmatrix_fill still writes the fp32 matrix (sq_fill_kernel) but takes the bit words from the O(N) inputs --
+                                      // sq_bits_masks_kernel, or sq_bits_direct_kernel as below -- instead of from the matrix (sq_bits_kernel)
     int host_threads = 0;             // SQ_HOST_THREADS: size of the batch's worker pool (0: by the CPUs)
 };
 void sq_read_batch_switches(SqBatchSwitches &sw);
@@ -70,7 +71,8 @@ struct SqTuning {
     uint32_t chain_depth = 3;         // SQ_CHAIN_DEPTH: chained rounds enqueued ahead of the device (at least 1)
     int pool_extend_waves = 1;        // SQ_POOL_EXTEND_WAVES: waves sharing a parent's children in the extend kernel on a crowded chip (1 .. 16)
     int fill_per = 0;                 // SQ_FILL_PER: 16-byte stores per thread of sq_fill_kernel's fast path (<= 0: by the launch)
-    bool bits_nomasks = false;        // SQ_BITS_NOMASKS: the cell-by-cell bit-matrix kernel for every batch
+    bool bits_nomasks = false;        // SQ_BITS_NOMASKS: sq_bits_direct_kernel (cell by cell) for every batch of the process in place of sq_bits_masks_kernel
+                                      // (without the switch: interchainonly batches and mask tables beyond 60 KB of LDS)
     bool no_state_scan_fuse = false;  // SQ_NO_STATE_SCAN_FUSE: state and scan kernel as two launches on a crowded chip
     int state_short_threads = 64;     // SQ_STATE_SHORT_THREADS: state-kernel threads for sequences up to 200 nt on a crowded chip (64 .. 256 in waves)
     bool state_short_set = false;     // ... given with another value than 64 (then the state and scan kernels are not fused)

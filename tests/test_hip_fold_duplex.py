@@ -15,8 +15,14 @@ T0 = "GGGGCUAAAAGCCCCAAAAAAUCAGGUCAUCG"
 TARGETS = [T0, random_seq(71, 64), random_seq(72, 90)]
 QUERIES = [revcomp(T0[2:14]), revcomp(TARGETS[1][20:34]), random_seq(73, 20), "A" * 10]
 SMALL = [random_seq(81, 40), random_seq(82, 65), random_seq(83, 30)], [random_seq(84, 21), revcomp(random_seq(82, 65)[10:31]), "U" * 12]
+# the screen at its ordinary size: duplexes of 278-323 nt, the list form of the pool round kernel on the bit words of
+# sq_bits_direct_kernel (several 256-diagonal tiles per word-row)
+LONG_TARGETS = [random_seq(91, 300), random_seq(92, 257)]
+LONG_QUERIES = [revcomp(LONG_TARGETS[0][140:162]), random_seq(93, 21), "A" * 20]
 
 CALLS = {"screen": lambda: (dict(targets=TARGETS, queries=QUERIES, configfile="greedynobpp"), TARGETS, QUERIES),
+         "interchainonly_long_targets": lambda: (dict(targets=LONG_TARGETS, queries=LONG_QUERIES, configfile="greedynobpp", interchainonly=True),
+                                                 LONG_TARGETS, LONG_QUERIES),
          "three_by_three_nobpp": lambda: (dict(targets=SMALL[0], queries=SMALL[1], configfile="nobpp"), SMALL[0], SMALL[1]),
          "interchainonly": lambda: (dict(targets=TARGETS, queries=QUERIES, configfile="greedynobpp", interchainonly=True), TARGETS, QUERIES)}
 
@@ -33,7 +39,7 @@ def test_result_stays_on_the_device_and_equals_the_cpu_built_one(tag):
     assert all(getattr(res, key).is_cuda for key in res._TENSORS)
     _, _, summary = check_result(res, targets, queries, pairs)
     assert any(s[0] > 0 for s in summary) and any(s[3] > 0 for s in summary)
-    if tag == "interchainonly":
+    if tag.startswith("interchainonly"):
         assert all(s[1] == 0 and s[2] == 0 for s in summary)
     if tag == "screen":
         assert summary[0][:4] == [12, 0, 0, 6] and all(summary[4 * a + 3][0] == 0 and summary[4 * a + 3][3] == 0 for a in range(3))

@@ -178,6 +178,27 @@ def test_algos_override_golden():
         assert same(got, unnan(c["out"])), (c["seq"], c["algos"])
 
 
+def test_interchain_golden():
+    """interchainonly beyond the 21 nt of bpmatrix.json (tests/golden/gen_interchain_golden.py): the stems of the chain-tested
+    matrix of four records up to 300 nt -- separators at the edges and on a word boundary, a restraint line -- and four folds
+    of multi-chain records, all exactly the reference's."""
+    from tests import bits_checks as B, interchain_checks as I
+    from tests.lowcomplex import check, digest
+    g = B.load_golden()
+    assert sorted(g["stems"]) == sorted(B.GOLDEN_RECORDS)
+    for name, exp in g["stems"].items():
+        m, stems = B.expected(B.RECORDS[B.NAMES.index(name)], 0, True)
+        assert [list(x) for x in stems] == exp and len(exp) > 40, name
+    assert [(c["tag"], c["config"]) for c in g["folds"]] == list(I.GOLDEN_FOLDS)
+    for c in g["folds"]:
+        case = I.find(c["tag"], c["config"])
+        assert (case["seq"], case["kw"]) == (c["seq"], c["kw"])
+        out = I.oracle_fold(I.case_id(case), True)
+        assert I.record_form(case, out) == c, I.case_id(c)          # (scores exactly, like every fixture of this file)
+        check(out, c)
+        assert digest(out[1]) == c["digest"] and c["nstruct"] >= 1 and "(" in c["cons"]
+
+
 def test_reference_form_of_the_oracle_equals_the_c_form():
     """oracle/sqrn_pyform.py -- the oracle's hot loops as interpreted per-cell Python, the form cpu_baseline.reference_form is
     timed in -- gives the tuples of the C form: short SRtest150 records under nobpp (G, N, E, H paramsets) and the example

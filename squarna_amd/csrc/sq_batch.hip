@@ -6,7 +6,6 @@
 // (ld - 1) / 32 odd, so that the byte stride between rows is an odd multiple of 128 B and consecutive rows
 // of a wave rotate through all memory channels instead of camping on a power-of-two stride
 // diagonal bit matrix of a job (sq_bits_kernel): nw word-rows of bpitch words
-static inline int32_t bits_nw(int n) { return (n + 31) / 32; }
 static inline int32_t bits_pitch(int n) { return (int32_t)align_up((size_t)2 * n, 64) + 64; }
 static inline int32_t ld_of(int n, const SqBatchSwitches &sw)
 {
@@ -119,7 +118,7 @@ JobNeed job_need(const sq_batch_desc *d, const Layout &L, int j)
     JobNeed q;
     const int s = d->job_seq[j], p = d->job_pset[j];
     q.n = d->seq_off[s + 1] - d->seq_off[s];
-    q.ld = ld_of(q.n, L.sw); q.nw = bits_nw(q.n); q.bpitch = bits_pitch(q.n);
+    q.ld = ld_of(q.n, L.sw); q.nw = sq_bits_nw(q.n); q.bpitch = bits_pitch(q.n);
     const bool ext = d->ext_score && d->ext_score[j];
     const bool own = d->mul_score && d->mul_score[j];
     const bool term = (d->bpp_term && d->bpp_term[j]) || dev_term(d, j);      // (formed on the device: booked like an uploaded one)

@@ -39,9 +39,8 @@ struct SqState {             // per-structure-slot arrays, `stride` elements per
 // kernel straight from pinned host memory (and mirrored into device memory for the later kernels), the
 // selected stems are written straight into pinned host memory, and a one-thread kernel at the end of the
 // round publishes the counters and a sequence number the host spins on.
-#ifndef SQ_SCORE_CHUNK
-#define SQ_SCORE_CHUNK 4          // candidates per thread and chunk of sq_score_kernel's two-phase loop
-#endif
+#include "sq_launch_lds.h"         // SQ_SCORE_CHUNK, the dynamic LDS layouts of the launched kernels, sq_extend_lds_bytes
+static_assert(sizeof(SqStrand) == SQ_STRAND_BYTES, "sq_score_lds places the strands by this size");
 
 struct SqRoundIO {
     const SqStruct *h_structs;   // pinned, host-written
@@ -283,16 +282,14 @@ __global__ void sq_scan6_kernel(SqDevCtx c, const SqStruct *structs, SqState stt
 __global__ void sq_state_scan_kernel(SqDevCtx c, SqRoundIO io, SqState stt, SqScanArgs a, int lds_n, int chained);
 __global__ void sq_bits_kernel(SqDevCtx c, int only_ext);
 __global__ void sq_score_kernel(SqDevCtx c, const SqStruct *structs, const SqStrand *strands, SqState stt,
-                                SqScanArgs a, SqRoundIO io, int lds_n, int lds_n_reacts, int lds_n_state, int surv_off, int cell_off,
-                                int str_off, int str_cap, SqCtxTab ct, int bound);
+                                SqScanArgs a, SqRoundIO io, SqScoreLds lo, SqCtxTab ct, int bound);
 __global__ void sq_bps_kernel(SqDevCtx c, const SqStruct *structs, const SqStrand *strands, SqState stt,
-                              SqScanArgs a, SqRoundIO io, int mode, int lds_n, int lds_n_reacts, int surv_off, int cell_off);
+                              SqScanArgs a, SqRoundIO io, int mode, SqScoreLds lo);
 __global__ void sq_select_kernel(SqDevCtx c, const SqStruct *structs, SqScanArgs a, SqRoundIO io);
 }
 
 // sq_extend.h: LDS of one structure's level scratch (chain / pool-extend kernels), lists of up to T stems
-#define SQ_CHAIN_TMAX 11264
-__host__ __device__ static inline size_t sq_extend_lds_bytes(int T) { const size_t t = ((size_t)T + 7) & ~(size_t)7; return t * 14 + 64 * 4 + 64; }
+#define SQ_CHAIN_TMAX 11264        // (sq_extend_lds_bytes(T): sq_launch_lds.h)
 
 // sq_gather.hip: the N x N weighting slices of the jobs in job_list from ONE shared L x L device matrix through the
 // per-position alignment columns (alignment step 2, SQRNdbnseq.py:1031-1034,1084-1085)

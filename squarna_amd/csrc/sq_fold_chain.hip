@@ -199,7 +199,7 @@ void SqFoldRun::chain_fold(LoopStats &stats)
                 if ((int)launched > maxt + 2) { fail(2, "chained rounds do not terminate"); break; }
                 // (algorithmic bytes: NOT per launch -- a launch also covers the structures that are already final; they are
                 // booked below from the evaluations the list of finished structures records)
-                sq_launch_round_kernels(b, st, S, maxn, maxcap, need_reacts, 0.0, 0, io, scan, ln.d_structs, b->chain.strands, true);
+                if (const int lr = sq_launch_round_kernels(b, st, S, maxn, maxcap, need_reacts, 0.0, 0, io, scan, ln.d_structs, b->chain.strands, true)) { fail(lr, sq_last_error()); break; }
                 const uint32_t seq = ++*ln.round_seq;
                 hipLaunchKernelGGL(sq_chain_done_kernel, dim3(1), dim3(1), 0, st, io, scan, b->chain, seq);
                 launched++;

@@ -167,7 +167,7 @@ int SqFoldRun::pool_fold(LoopStats &stats)
                 pra.parity = par_l; pra.ahead = 1;
                 for (int lo = 0; lo < slots; lo += chunk) {
                     pra.lo = lo;
-                    sq_launch_round_kernels(b, st, std::min(chunk, slots - lo), maxn, maxcap, need_reacts, 0.0, 0, io, scan, pio.structs + (size_t)par_l * pio.smax + lo, pio.strands, true, true, &pra);
+                    if (const int lr = sq_launch_round_kernels(b, st, std::min(chunk, slots - lo), maxn, maxcap, need_reacts, 0.0, 0, io, scan, pio.structs + (size_t)par_l * pio.smax + lo, pio.strands, true, true, &pra)) return fail(lr, sq_last_error());
                 }
                 const uint32_t seq = ++*ln.round_seq;
                 hipLaunchKernelGGL(sq_pool_scan_kernel, dim3(1), dim3(1024), 0, st, pio, scan, io, par_l, seq);
@@ -197,8 +197,8 @@ int SqFoldRun::pool_fold(LoopStats &stats)
         for (int lo = 0; lo < S; lo += chunk) {              // (stream order: a chunk's chosen stems are out before the next one reuses the arena)
             io.h_structs = cur + lo; io.d_structs = cur + lo;
             pra.parity = parity; pra.lo = lo;
-            sq_launch_round_kernels(b, st, std::min(chunk, S - lo), maxn, maxcap, need_reacts, 0.0, 0, io, scan, cur + lo, pio.strands, true, true,
-                                 round_kernel ? &pra : nullptr);
+            if (const int lr = sq_launch_round_kernels(b, st, std::min(chunk, S - lo), maxn, maxcap, need_reacts, 0.0, 0, io, scan, cur + lo, pio.strands, true, true,
+                                                       round_kernel ? &pra : nullptr)) return fail(lr, sq_last_error());
         }
         const uint32_t seq = ++*ln.round_seq;
         hipLaunchKernelGGL(sq_pool_scan_kernel, dim3(1), dim3(b->inflight > 1 ? 256 : 1024), 0, st, pio, scan, io, parity, seq);

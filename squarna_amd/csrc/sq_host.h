@@ -253,6 +253,9 @@ int sq_check(hipError_t e, const char *what);
 // hipFuncAttributeMaxDynamicSharedMemorySize of `fn` on the CURRENT device, set once per (kernel, device): the
 // attribute is per device and a process may fold on several (one worker thread per batch); thread-safe
 void sq_max_dynamic_lds(const void *fn, int bytes);
+// may `fn` be launched with `bytes` of dynamic LDS?  Raises the kernel's limit when the launch needs it (above 64 KB); false: more
+// than a CU has (the launch sites whose kernels hold static LDS as well keep their own, lower thresholds)
+bool sq_dynamic_lds_ok(const void *fn, size_t bytes);
 int sq_effective_cpus();                       // CPUs this process may really use: hardware threads, affinity, cgroup quota
 bool sq_relaxed_waits(const sq_batch *b);       // spin-then-sleep instead of pure spinning (many batches in flight, few CPUs)
 void sq_wait_step(uint64_t spins, bool relaxed);   // one step of a wait loop on a pinned completion word

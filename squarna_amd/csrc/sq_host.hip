@@ -39,6 +39,13 @@ void sq_max_dynamic_lds(const void *fn, int bytes)
     done.emplace_back(fn, dev);
 }
 
+bool sq_dynamic_lds_ok(const void *fn, size_t bytes)
+{
+    if (!sq_lds_fits(bytes)) return false;
+    if (sq_lds_needs_raise(bytes)) sq_max_dynamic_lds(fn, SQ_LDS_BLOCK_MAX);
+    return true;
+}
+
 int sq_effective_cpus()
 {
     static const int n = [] {

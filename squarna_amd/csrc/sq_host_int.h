@@ -76,7 +76,7 @@ extern "C" __global__ void sq_fill_f64_kernel(double *dst, long long n, double v
 
 // sq_round_host.hip
 int sq_fill_impl(sq_batch *b, int full);
-void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64_t maxcap, bool need_reacts, double scan_bytes,
+int sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64_t maxcap, bool need_reacts, double scan_bytes,
                              int mode, const SqRoundIO &io, const SqScanArgs &scan, SqStruct *d_structs, SqStrand *d_strands,
                              bool chained, bool pooled = false, const SqPoolRoundArgs *pool_round = nullptr);
 int sq_run_round_impl(sq_batch *b, SqLane &ln, const std::vector<SView> &structs, int mode,

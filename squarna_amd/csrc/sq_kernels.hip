@@ -26,13 +26,12 @@
 // ------------------------------------------------------------------------------------
 // a-1  fill: one thread = 4 consecutive floats of the padded N x ld matrix (16-byte stores)
 // ------------------------------------------------------------------------------------
-// Jobs without a dense fp64 term and with n <= SQ_FILL_LDS_N take the fast path: the per-position inputs (letter code +
+// Jobs without a dense fp64 term and with n <= SQ_FILL_LDS_N (sq_launch_lds.h) take the fast path: the per-position inputs (letter code +
 // restraint flags in one byte, minimal span, chain, reactivity) and the pair-weight table are staged in LDS once per
 // block, a thread then walks the flat padded matrix with a grid stride (row / column advanced incrementally: no 64-bit
 // division per store) and a cell costs two LDS byte reads, one table read and a handful of compares before the
 // 16-byte store.  The generic path (every input from global memory, per cell) serves jobs with a bpp term / multiplier
 // matrix and very long sequences.
-#define SQ_FILL_LDS_N 4096
 extern "C" __global__ __launch_bounds__(256) void sq_fill_kernel(SqDevCtx c, int only_ext, int mul_done)
 {
     const SqJob jb = c.jobs[blockIdx.y];
@@ -43,14 +42,14 @@ extern "C" __global__ __launch_bounds__(256) void sq_fill_kernel(SqDevCtx c, int
     const int n = jb.n, ld = jb.ld;
     float *mat = c.mat32 + jb.mat_off;
     extern __shared__ __attribute__((aligned(16))) char fill_dyn[];
-    if (jb.mat64_off < 0 && !jb.mulsh && n <= SQ_FILL_LDS_N) {
+    if (jb.mat64_off < 0 && !jb.mulsh && sq_fill_staged(n)) {
         __shared__ double s_w[32 * 33];                // pair weights, row stride 33: the letters' rows start on different banks
         __shared__ float s_wf[32 * 33];                // (float)weight, or the sentinel where the pair is not in bps
-        const int np = (n + 15) & ~15;
-        uint8_t *l_attr = reinterpret_cast<uint8_t *>(fill_dyn);            // code | flags << 5
-        uint8_t *l_inc4 = l_attr + np;
-        int16_t *l_chain = reinterpret_cast<int16_t *>(l_inc4 + np);
-        double *l_react = reinterpret_cast<double *>(l_inc4 + np + 2 * (size_t)np);
+        const SqFillLds lo = sq_fill_lds(n);                                // by the JOB: inside the launch's room for its longest staged job
+        uint8_t *l_attr = reinterpret_cast<uint8_t *>(fill_dyn + lo.attr);  // code | flags << 5
+        uint8_t *l_inc4 = reinterpret_cast<uint8_t *>(fill_dyn + lo.inc4);
+        int16_t *l_chain = reinterpret_cast<int16_t *>(fill_dyn + lo.chain);
+        double *l_react = reinterpret_cast<double *>(fill_dyn + lo.react);
         const int tid = threadIdx.x;
         const bool ico = jb.interchainonly != 0, defr = jb.default_reacts != 0;
         for (int p = tid; p < n; p += 256) {
@@ -303,16 +302,17 @@ extern "C" __global__ __launch_bounds__(256) void sq_bits_masks_kernel(SqDevCtx 
     __shared__ uint8_t s_letter[32];
     const SqJob jb = c.jobs[blockIdx.y];
     if (jb.has_ext == 1 || !jb.bits_owner) return;      // bool comes from the caller's matrix (sq_bits_kernel) / from an earlier job of the sequence
-    const int n = jb.n, bp = jb.bpitch, nw = jb.nw, mw = nw + 3;
+    const int n = jb.n, bp = jb.bpitch, nw = jb.nw;
     const SqPsetDev *ps = c.psets + jb.pset;
     uint32_t *bits = c.bits + jb.bits_off;
     const int tid = threadIdx.x;
-    const int npad = (n + 3) & ~3;
-    uint8_t *s_ccode = reinterpret_cast<uint8_t *>(s_bm);               // [npad] column letter (31 = excluded)
-    uint8_t *s_rcode = s_ccode + npad;                                  // [npad] row letter (31 = excluded)
-    uint8_t *s_inc = s_rcode + npad;                                    // [npad] minimal j - i
-    uint32_t *s_M = reinterpret_cast<uint32_t *>(s_inc + npad);         // [max_letters][mw], one zero word in front
-    uint32_t *s_R = s_M + max_letters * mw;                             // [nw][max_letters]
+    const SqMasksLds lo = sq_bits_masks_lds(n, max_letters);            // by the JOB (jb.nw == lo.nw), with the launch's letters
+    uint8_t *s_ccode = reinterpret_cast<uint8_t *>(s_bm + lo.ccode);    // [npad] column letter (31 = excluded)
+    uint8_t *s_rcode = reinterpret_cast<uint8_t *>(s_bm + lo.rcode);    // [npad] row letter (31 = excluded)
+    uint8_t *s_inc = reinterpret_cast<uint8_t *>(s_bm + lo.inc);        // [npad] minimal j - i
+    uint32_t *s_M = reinterpret_cast<uint32_t *>(s_bm + lo.M);          // [max_letters][mw], one zero word in front
+    uint32_t *s_R = reinterpret_cast<uint32_t *>(s_bm + lo.R);          // [nw][max_letters]
+    const int mw = lo.mw;
     if (tid < 32) s_pm[tid] = ps->pmask[tid];           // :300 (codes 0..28; 31 never set) -- from the host: one load instead of 29 byte loads behind branches
     if (tid == 0) s_present = 0;
     __syncthreads();
@@ -465,10 +465,8 @@ __device__ __forceinline__ bool sq_state_body(const SqDevCtx &c, const SqRoundIO
     const SqStrand *sd = io.d_strands + s.strand_off;
     const int n = jb.n;
     if (n <= lds_n) {
-        const int np = (lds_n + 8) & ~7;                  // arrays of n + 1 entries, 8-byte aligned sections
-        int16_t *P = reinterpret_cast<int16_t *>(st_dyn), *U = P + np, *SU = U + np;
-        uint8_t *E = reinterpret_cast<uint8_t *>(SU + np);
-        sq_state_build<true>(c, s, jb, sd, st, P, E, U, SU);
+        const SqStateArrays A = sq_state_carve(st_dyn, sq_state_lds(lds_n));   // by the LAUNCH: arrays of n + 1 entries, 8-byte aligned sections
+        sq_state_build<true>(c, s, jb, sd, st, A.P, A.E, A.U, A.SU);
     } else {
         sq_state_build<false>(c, s, jb, sd, st, st.P + (int64_t)s.slot * st.stride, st.E8 + (int64_t)s.slot * st.stride * 2,
                               st.U + (int64_t)s.slot * st.stride, st.SU + (int64_t)s.slot * st.stride);
@@ -559,7 +557,7 @@ struct SqScan6Sink {
 __device__ __forceinline__ void sq_scan6_body(const SqDevCtx &c, const SqStruct &st, const SqState &stt, SqScanArgs &a, int gy0, int gystep)
 {
     __shared__ __attribute__((aligned(16))) SqScan6Lds L;
-    extern __shared__ uint32_t sq6_fg[];                                // F words then G words of the structure
+    extern __shared__ uint32_t sq6_fg[];                                // F words then G words of the structure (sq_scan6_lds)
     if (st.nstrand < 0) return;                                         // (chained rounds) the structure is final
     const SqJob jb = c.jobs[st.job];
     const int n = jb.n;
@@ -603,8 +601,6 @@ extern "C" __global__ __launch_bounds__(64) void sq_state_scan_kernel(SqDevCtx c
 // ------------------------------------------------------------------------------------
 // a-4..a-6  exact rescoring + ScoreStems closed form + range filter (one block per structure)
 // ------------------------------------------------------------------------------------
-#define SQ_LDS_STRANDS 1024
-
 #include "sq_score.h"
 
 #ifndef SQ_DIAG_TOGETHER
@@ -615,8 +611,7 @@ extern "C" __global__ __launch_bounds__(64) void sq_state_scan_kernel(SqDevCtx c
 #endif
 template <bool FULL>
 __device__ __forceinline__ void sq_score_body(const SqDevCtx &c, const SqStruct *structs, const SqStrand *strands,
-                                              const SqState &stt, SqScanArgs &a, const SqRoundIO &io, int mode, int lds_n,
-                                              int lds_n_reacts, int lds_n_state, int surv_off, int cell_off, int str_off = 0, int str_cap = 0,
+                                              const SqState &stt, SqScanArgs &a, const SqRoundIO &io, int mode, const SqScoreLds &lo,
                                               const SqCtxTab ct = SqCtxTab{}, int bound = 1)
 {
     // (the structure's strands and their skip pointers live in the block's DYNAMIC LDS, sized by the host for the longest
@@ -635,9 +630,10 @@ __device__ __forceinline__ void sq_score_body(const SqDevCtx &c, const SqStruct 
     // largest K R of the batch (25 entries for ACGU without reactivity levels; a static 32 x 33 array cost 8 KB per block).
     __shared__ uint8_t s_cls[32];
     extern __shared__ __attribute__((aligned(16))) char s_dyn[];   // letter codes [n] (+ reactivities [n] when they fit)
-    double *const s_cell = reinterpret_cast<double *>(s_dyn + cell_off);
-    SqStrand *const s_str = reinterpret_cast<SqStrand *>(s_dyn + str_off);
-    uint16_t *const s_skip = reinterpret_cast<uint16_t *>(s_str + str_cap);   // 5' strand k closes a block: next strand that can matter after it
+    const int str_cap = lo.str_cap;
+    double *const s_cell = reinterpret_cast<double *>(s_dyn + lo.cell);
+    SqStrand *const s_str = reinterpret_cast<SqStrand *>(s_dyn + lo.str);
+    uint16_t *const s_skip = reinterpret_cast<uint16_t *>(s_dyn + lo.skip);   // 5' strand k closes a block: next strand that can matter after it
     const SqStruct st = structs[blockIdx.x];
 #ifdef SQ_SCORE_PROF
     const long long _p0 = wall_clock64(); long long _pa = 0, _pb = 0, _ps = 0;
@@ -673,12 +669,13 @@ __device__ __forceinline__ void sq_score_body(const SqDevCtx &c, const SqStruct 
     const int16_t *U = stt.U + (int64_t)st.slot * stt.stride;
     const int16_t *SU = stt.SU + (int64_t)st.slot * stt.stride;
     // the exact re-scoring touches codes / weights / reactivities once per cell: keep them in LDS
-    double *l_reacts = reinterpret_cast<double *>(s_dyn + ((n + 15) & ~15));
+    const SqScoreJobLds jl = sq_score_lds_job(lo, n);                   // what this JOB stages by its own length, and whether it has room
+    double *l_reacts = reinterpret_cast<double *>(s_dyn + jl.reacts);
     // ScoreStems walks the partner array and reads the prefix counts with dependent loads: LDS copies when they
     // fit (3 x int16 per position, after the codes and reactivities of the launch's longest sequence)
-    if (mode == 0 && lds_n_state >= n) {
-        int16_t *lP = reinterpret_cast<int16_t *>(s_dyn + ((lds_n + 15) & ~15) + (size_t)8 * lds_n_reacts);
-        int16_t *lU = lP + ((lds_n_state + 8) & ~7), *lSU = lU + ((lds_n_state + 8) & ~7);
+    if (mode == 0 && jl.state_fits) {
+        int16_t *lP = reinterpret_cast<int16_t *>(s_dyn + lo.P), *lU = reinterpret_cast<int16_t *>(s_dyn + lo.U);
+        int16_t *lSU = reinterpret_cast<int16_t *>(s_dyn + lo.SU);
         // 32-bit copies (the arrays start 64-byte aligned: stride is a multiple of 32 positions)
         const uint32_t *gP = reinterpret_cast<const uint32_t *>(P), *gU = reinterpret_cast<const uint32_t *>(U);
         const uint32_t *gS = reinterpret_cast<const uint32_t *>(SU);
@@ -687,7 +684,7 @@ __device__ __forceinline__ void sq_score_body(const SqDevCtx &c, const SqStruct 
         for (int q = tid; q < nw2; q += nthr) { wP[q] = gP[q]; wU[q] = gU[q]; wS[q] = gS[q]; }
         P = lP; U = lU; SU = lSU;
     }
-    const bool lds_cells = jb.mat64_off < 0 && !jb.mulsh && lds_n >= n;
+    const bool lds_cells = jb.mat64_off < 0 && !jb.mulsh && jl.ci_fits;
     const bool any_reacts = lds_cells && !jb.default_reacts;
     // classes of the letters: K pairing letters + one class for everything else.  lmask: bit a set iff letter a has a
     // pair in the paramset (row a of inbps is not all zero) -- the first 32 threads test a row each, one ballot
@@ -707,12 +704,12 @@ __device__ __forceinline__ void sq_score_body(const SqDevCtx &c, const SqStruct 
     const int K = __popc(lmask) + 1;
     // few distinct reactivity values (encoded input): level index per position, reactfactors folded into the table
     const bool react_tab = any_reacts && jb.react_levels > 0 && K * jb.react_levels <= 32;   // (the host sizes LDS by the same rule)
-    const bool lds_reacts = any_reacts && !react_tab && lds_n_reacts >= n;                    // per-cell factors from LDS copies
+    const bool lds_reacts = any_reacts && !react_tab && jl.reacts_fit;                    // per-cell factors from LDS copies
     const int R = react_tab ? jb.react_levels : 1;
     const int KR = K * R, cstride = KR | 1;
     const bool cell_tab = lds_cells && (jb.default_reacts || react_tab);     // the table holds the final cell value
     __shared__ double s_rv[16];
-    uint8_t *l_ci = reinterpret_cast<uint8_t *>(s_dyn);                       // combined index per position
+    uint8_t *l_ci = reinterpret_cast<uint8_t *>(s_dyn + jl.ci);                       // combined index per position
     if (lds_cells) {
         if (tid < 32) s_cls[tid] = (lmask >> tid) & 1u ? (uint8_t)__popc(lmask & ((1u << tid) - 1u)) : (uint8_t)(K - 1);
         if (react_tab)
@@ -891,9 +888,9 @@ __device__ __forceinline__ void sq_score_body(const SqDevCtx &c, const SqStruct 
         // survivors of a chunk of SQ_SCORE_CHUNK x blockDim candidates are gathered in LDS and written out with ONE
         // global atomic per block and chunk: all blocks of a structure append to the same counter, and one atomic
         // per wave made that counter the bottleneck of long sequences (A5000: 3.2 -> 0.6 ms per 47 sequences).
-        double *s_bps = reinterpret_cast<double *>(s_dyn + surv_off);
-        uint32_t *s_key = reinterpret_cast<uint32_t *>(s_bps + SQ_SCORE_CHUNK * nthr);
-        uint16_t *s_len = reinterpret_cast<uint16_t *>(s_key + SQ_SCORE_CHUNK * nthr);
+        double *s_bps = reinterpret_cast<double *>(s_dyn + lo.surv_bps);
+        uint32_t *s_key = reinterpret_cast<uint32_t *>(s_dyn + lo.surv_key);
+        uint16_t *s_len = reinterpret_cast<uint16_t *>(s_dyn + lo.surv_len);
         __shared__ uint32_t s_n, s_base;
         if (tid == 0) s_n = 0;
         __syncthreads();
@@ -949,9 +946,9 @@ __device__ __forceinline__ void sq_score_body(const SqDevCtx &c, const SqStruct 
     // candidates (cheap: LDS only) and the ones that pass :492 are appended to a list in LDS; (B) ScoreStems runs on
     // FULL groups of blockDim survivors (its chain of dependent loads is what the kernel waits for, so lanes idling
     // on rejected candidates were the cost); the remainder (< blockDim) is carried into the next chunk.
-    double *s_bps = reinterpret_cast<double *>(s_dyn + surv_off);
-    uint32_t *s_key = reinterpret_cast<uint32_t *>(s_bps + (SQ_SCORE_CHUNK + 1) * nthr);
-    uint16_t *s_len = reinterpret_cast<uint16_t *>(s_key + (SQ_SCORE_CHUNK + 1) * nthr);
+    double *s_bps = reinterpret_cast<double *>(s_dyn + lo.surv_bps);
+    uint32_t *s_key = reinterpret_cast<uint32_t *>(s_dyn + lo.surv_key);
+    uint16_t *s_len = reinterpret_cast<uint16_t *>(s_dyn + lo.surv_len);
     __shared__ uint32_t s_nsurv, s_okn;
     // Branch and bound.  Every reader of the survivor list keeps only finalscores >= subopt x best (:769-778; width-1
     // chains and the stopper :1147 only the best itself), and a candidate's finalscore cannot exceed
@@ -1102,19 +1099,17 @@ __device__ __forceinline__ void sq_score_body(const SqDevCtx &c, const SqStruct 
 // mode 0 (the greedy rounds): bpscore filter + ScoreStems, two phases (see the body)
 extern "C" __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(SQ_SCORE_WAVES))) void sq_score_kernel(SqDevCtx c, const SqStruct *structs,
                                                                   const SqStrand *strands, SqState stt, SqScanArgs a,
-                                                                  SqRoundIO io, int lds_n, int lds_n_reacts, int lds_n_state, int surv_off,
-                                                                  int cell_off, int str_off, int str_cap, SqCtxTab ct, int bound)
+                                                                  SqRoundIO io, SqScoreLds lo, SqCtxTab ct, int bound)
 {
-    sq_score_body<true>(c, structs, strands, stt, a, io, 0, lds_n, lds_n_reacts, lds_n_state, surv_off, cell_off, str_off, str_cap, ct, bound);
+    sq_score_body<true>(c, structs, strands, stt, a, io, 0, lo, ct, bound);
 }
 
 // modes 1 / 2 (OptimalStems output, alignment survivor list): the bpscore filter alone, as its own kernel so that its
 // loop is not compiled under the register budget of ScoreStems
 extern "C" __global__ __launch_bounds__(1024) void sq_bps_kernel(SqDevCtx c, const SqStruct *structs, const SqStrand *strands,
-                                                                SqState stt, SqScanArgs a, SqRoundIO io, int mode, int lds_n,
-                                                                int lds_n_reacts, int surv_off, int cell_off)
+                                                                SqState stt, SqScanArgs a, SqRoundIO io, int mode, SqScoreLds lo)
 {
-    sq_score_body<false>(c, structs, strands, stt, a, io, mode, lds_n, lds_n_reacts, 0, surv_off, cell_off);
+    sq_score_body<false>(c, structs, strands, stt, a, io, mode, lo);
 }
 
 // ChooseStems range filter (:769-778): candidates within subopt * best of the structure's best finalscore

@@ -48,13 +48,14 @@ extern "C" __global__ __launch_bounds__(256) void sq_pool_init_kernel(const SqSt
 
 extern "C" __global__ __launch_bounds__(64) void sq_pool_choose_kernel(SqDevCtx c, const SqStruct *structs, SqScanArgs a, SqPoolIO pio, int nsurv)
 {
-    // the survivors within the range, sorted in LDS: room for `nsurv` of them (18 bytes each) in the block's dynamic LDS --
+    // the survivors within the range, sorted in LDS: room for `nsurv` of them (sq_pool_choose_lds) in the block's dynamic LDS --
     // 1,024 for long sequences, fewer for short ones (a block's LDS is LDS its neighbours on the CU cannot get); a
     // structure with more survivors in range raises the overflow flag and the host repeats the fold with its own loop
     extern __shared__ __attribute__((aligned(16))) char sq_choose_dyn[];
-    double *const s_fin = reinterpret_cast<double *>(sq_choose_dyn);
-    uint32_t *const s_q = reinterpret_cast<uint32_t *>(s_fin + nsurv), *const s_key = s_q + nsurv;
-    uint16_t *const s_ord = reinterpret_cast<uint16_t *>(s_key + nsurv);
+    const SqChooseLds lo = sq_pool_choose_lds(nsurv);
+    double *const s_fin = reinterpret_cast<double *>(sq_choose_dyn + lo.fin);
+    uint32_t *const s_q = reinterpret_cast<uint32_t *>(sq_choose_dyn + lo.q), *const s_key = reinterpret_cast<uint32_t *>(sq_choose_dyn + lo.key);
+    uint16_t *const s_ord = reinterpret_cast<uint16_t *>(sq_choose_dyn + lo.ord);
     __shared__ int s_ri[SQ_POOL_CMAX], s_rj[SQ_POOL_CMAX], s_rl[SQ_POOL_CMAX];
     const int lane = threadIdx.x;
     const SqStruct st = structs[blockIdx.x];                // (structs: the chunk of the round's list this launch covers)

@@ -14,7 +14,7 @@ int sq_fill_impl(sq_batch *b, int full)
         maxw = std::max<int64_t>(maxw, (int64_t)J.nw * ((J.bpitch + 255) / 256));
         if (full || J.has_ext) bytes += 4.0 * J.n * J.n;                // algorithmic: one fp32 N x N write
         any_ext1 |= J.has_ext == 1; any_ext |= J.has_ext != 0;
-        if (J.n <= 4096) maxlds = std::max(maxlds, (int)J.n);       // (SQ_FILL_LDS_N: the longest job the fill may stage in LDS)
+        if (sq_fill_staged(J.n)) maxlds = std::max(maxlds, (int)J.n);   // (the longest job the fill may stage in LDS)
     }
     for (int j0 = 0; j0 < b->njobs; j0 += 32768) {
         const int nj = std::min(32768, b->njobs - j0);
@@ -22,16 +22,16 @@ int sq_fill_impl(sq_batch *b, int full)
         dim3 grid((unsigned)std::min<int64_t>(std::max<int64_t>((maxq + 255) / 256, 1), 1024), (unsigned)nj);
         if (full || any_ext) {
             ProfScope ps(b, 0, j0 == 0 ? bytes : 0);
-            // the fill's fast path stages the O(N) inputs in LDS (12 bytes per position) when the longest sequence fits;
+            // the fill's fast path stages the O(N) inputs in LDS (sq_fill_lds) when the longest sequence fits;
             // its blocks are fewer and fatter than the generic path's so that the staging is amortised
-            const bool lds_inputs = b->maxn <= 4096;
+            const bool lds_inputs = sq_fill_staged(b->maxn);
             // 16-byte stores per thread: as many as leave ~4096 blocks in the launch (the LDS staging of a block is amortised over them)
             const int fper_env = sq_tuning().fill_per;
             const int64_t fper = 256 * (fper_env > 0 ? (int64_t)fper_env
                                                      : std::min<int64_t>(std::max<int64_t>(maxq * nj / (256 * 4096), 4), 64));
             // (the kernel picks its path per JOB: a batch whose longest sequence is beyond SQ_FILL_LDS_N still stages its shorter
             // jobs in LDS, so the room is that of the longest job that may take the path, not 0)
-            const size_t fdyn = maxlds ? (size_t)12 * ((maxlds + 15) & ~15) + 64 : 0;
+            const size_t fdyn = maxlds ? sq_fill_lds(maxlds).total : 0;
             dim3 fgrid(lds_inputs ? (unsigned)std::min<int64_t>(std::max<int64_t>((maxq + fper - 1) / fper, 1), 1024) : grid.x, (unsigned)nj);
             hipLaunchKernelGGL(sq_fill_kernel, fgrid, dim3(256), fdyn, b->stream, c, full ? 0 : 1, b->mul_applied ? 1 : 0);
         }
@@ -44,12 +44,11 @@ int sq_fill_impl(sq_batch *b, int full)
             if (j0 == 0 && !(full || any_ext)) for (const SqJob &J : b->jobs) bbytes += 4.0 * J.nw * J.bpitch;   // bit words written
             ProfScope ps(b, 0, bbytes);
             // letter-mask formulation unless the chain test is on or the O(N) tables outgrow LDS
-            const int nwmax = (b->maxn + 31) / 32;
-            const size_t mdyn = 3 * (size_t)((b->maxn + 3) & ~3) + 4 * (size_t)b->nletters * (nwmax + 3) + 4 * (size_t)nwmax * b->nletters + 16;
+            const SqMasksLds mlo = sq_bits_masks_lds(b->maxn, b->nletters);
             const bool no_masks = sq_tuning().bits_nomasks;
-            if (!b->interchainonly && !no_masks && b->nletters > 0 && mdyn <= 60 * 1024) {
-                const int bparts = std::max(1, std::min(nwmax, (2048 + nj - 1) / nj));
-                hipLaunchKernelGGL(sq_bits_masks_kernel, dim3(bparts, nj), dim3(256), mdyn, b->stream, c, b->nletters);
+            if (!b->interchainonly && !no_masks && b->nletters > 0 && sq_bits_masks_fit(mlo)) {
+                const int bparts = std::max(1, std::min(mlo.nw, (2048 + nj - 1) / nj));
+                hipLaunchKernelGGL(sq_bits_masks_kernel, dim3(bparts, nj), dim3(256), mlo.total, b->stream, c, b->nletters);
             } else
                 hipLaunchKernelGGL(sq_bits_direct_kernel, g2, dim3(256), 0, b->stream, c);
         }
@@ -208,8 +207,9 @@ void sq_extend_struct(const HStruct &parent, const HStem &stem, HStruct &child, 
 
 // ---- round driver ---------------------------------------------------------------------------
 // the kernels of one round over S structures: state arrays, bit-diagonal scan, exact scoring (mode 0: + ScoreStems),
-// and for host-driven greedy rounds the range filter that writes the round's output records
-void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64_t maxcap, bool need_reacts, double scan_bytes,
+// and for host-driven greedy rounds the range filter that writes the round's output records.  Nonzero (with sq_last_error set): the
+// scoring kernel's LDS does not fit a CU -- the round is not complete and must not be waited for.
+int sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64_t maxcap, bool need_reacts, double scan_bytes,
                              int mode, const SqRoundIO &io, const SqScanArgs &scan, SqStruct *d_structs, SqStrand *d_strands,
                              bool chained, bool pooled, const SqPoolRoundArgs *pool_round)
 {
@@ -224,11 +224,11 @@ void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64
         ProfScope ps(b, 3, scan_bytes);
         if (pool_round->root) hipLaunchKernelGGL(sq_pool_round_root_kernel, dim3(S), dim3(64), lo.total, st, b->ctx, scan, b->pool_io, *pool_round);
         else hipLaunchKernelGGL(sq_pool_round_kernel, dim3(S), dim3(64), lo.total, st, b->ctx, scan, b->pool_io, *pool_round);
-        return;
+        return 0;
     }
     if (fuse) {
         ProfScope ps(b, 2, scan_bytes);
-        const size_t dyn_state = (size_t)7 * ((maxn + 8) & ~7) + 64, dyn_scan = 4 * (size_t)b->state.fbstride;
+        const size_t dyn = sq_state_scan_lds(maxn, b->state.fbstride).total;     // (the state arrays, then the scan words in their place)
         // (the structure records go to the device by ONE copy first: read from the pinned array by every wave, each of the
         // launch's thousands of waves began with a read over PCIe -- 3.0 -> 1.2 G wave cycles per three headline steps,
         // the headline +1.6 %; SQ_NO_STATE_COPY: the old form)
@@ -238,13 +238,13 @@ void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64
             hipMemcpyAsync(io.d_structs, io.h_structs, (size_t)S * sizeof(SqStruct), hipMemcpyHostToDevice, st);
             io2.h_structs = io.d_structs;
         }
-        hipLaunchKernelGGL(sq_state_scan_kernel, dim3(S), dim3(64), std::max(dyn_state, dyn_scan), st, b->ctx, io2, b->state, scan, maxn, chained ? 1 : 0);
+        hipLaunchKernelGGL(sq_state_scan_kernel, dim3(S), dim3(64), dyn, st, b->ctx, io2, b->state, scan, maxn, chained ? 1 : 0);
     }
     if (!fuse) {
         ProfScope ps(b, 1, 0);
-        // the per-structure arrays are assembled in LDS (7 bytes per position) when the longest sequence fits
-        const int st_lds_n = maxn <= 8000 ? maxn : 0;
-        const size_t st_dyn = st_lds_n ? (size_t)7 * ((st_lds_n + 8) & ~7) + 64 : 0;
+        // the per-structure arrays are assembled in LDS (sq_state_lds) when the longest sequence fits
+        const int st_lds_n = sq_state_lds_n(maxn);
+        const size_t st_dyn = sq_state_lds(st_lds_n).total;
         // (sequences up to 200 nt: one wave builds the arrays in three or four steps; four waves per structure held four
         // times the wave slots for the same few microseconds -- with batches in flight the chip is short of exactly those)
         // "crowded": the chip is (or will be) short of wave slots -- several batches in flight, or a batch of four thousand
@@ -263,23 +263,19 @@ void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64
         // (sequences up to 200 nt: one wave per structure walks all its diagonal groups, see the kernel)
         const int scan_short = tu.scan_short_waves;
         const int scan_groups = (2 * maxn - 5 + 63) / 64 + 1;
-        hipLaunchKernelGGL(sq_scan6_kernel, dim3(S, maxn <= 200 && crowded ? std::min(scan_short, scan_groups) : scan_groups), dim3(64), 4 * (size_t)b->state.fbstride, st,
+        hipLaunchKernelGGL(sq_scan6_kernel, dim3(S, maxn <= 200 && crowded ? std::min(scan_short, scan_groups) : scan_groups), dim3(64), sq_scan6_lds(b->state.fbstride), st,
                            b->ctx, d_structs, b->state, scan);
     }
     {
         ProfScope ps(b, 3, 0);
-        // dynamic LDS: letter codes of the longest sequence, plus its reactivities when they fit in 32 KiB
-        const int lds_n = maxn <= 16384 ? maxn : 0;
-        const int nr_lim = tu.score_nr_lim;
+        // dynamic LDS (sq_score_lds): letter codes of the longest sequence, plus its reactivities when they fit in 32 KiB
+        const int lds_n = sq_score_lds_n(maxn);
         // (only when some job needs them: sequences whose reactivities go through the cell table leave the room to the
         // partner / prefix arrays -- S2000 with encoded SHAPE: 16 KB that pushed those arrays out to global memory)
-        const int lds_nr = need_reacts && maxn <= nr_lim ? maxn : 0;
+        const int lds_nr = sq_score_lds_nr(maxn, need_reacts, tu.score_nr_lim);
         // partner / prefix arrays (3 x int16) too, while a block stays small enough for four blocks per CU
         // (the reactivity case is bound by fp64 sqrt/div throughput and prefers the occupancy)
-        const size_t state_lim = tu.score_state_lim;
-        const size_t dyn_base = lds_n ? (size_t)((lds_n + 15) & ~15) + (size_t)8 * lds_nr + 16 : 0;
-        const int lds_ns = (lds_n && mode == 0 && dyn_base + (size_t)6 * ((maxn + 8) & ~7) <= state_lim) ? maxn : 0;
-        size_t dyn = lds_n ? (size_t)((lds_n + 15) & ~15) + (size_t)8 * lds_nr + (size_t)6 * ((lds_ns + 8) & ~7) + 16 : 0;
+        const int lds_ns = sq_score_lds_ns(lds_n, lds_nr, maxn, mode, tu.score_state_lim);
         // few structures: deal each structure's candidates to several blocks so that the launch still fills the chip
         const int score_threads = tu.score_threads, score_parts = tu.score_parts, score_target = tu.score_target;
         // mode 0 (two-phase loop): ~512 blocks of 512 threads; the one-pass modes want many small blocks in flight
@@ -296,40 +292,37 @@ void sq_launch_round_kernels(sq_batch *b, hipStream_t st, int S, int maxn, int64
         const int thr0 = maxn <= 200 ? (crowded ? short_thr : 128) : (pooled && S >= 2048 ? std::min(pooled_thr, maxn <= 400 ? 256 : 512) : (maxn <= 400 ? 256 : 512));
         // (the one-pass modes on a crowded chip: a structure of a short sequence has ~150 candidates -- one wave, not four)
         const int thr = score_threads ? score_threads : (mode == 0 ? thr0 : (maxn <= 200 && crowded ? 64 : (parts == 1 && S < 2048 ? 512 : 256)));
-        // the cell table (K R x (K R | 1) doubles for the batch's largest K R), then
-        // mode 0: list of the bpscore survivors of a chunk (5 x threads entries of 8 + 4 + 2 bytes) behind the tables
-        const int cell_off = (int)((dyn + 15) & ~(size_t)15);
-        dyn = (size_t)cell_off + 8 * (size_t)b->cell_entries;
-        const int surv_off = (int)((dyn + 15) & ~(size_t)15);
-        dyn = (size_t)surv_off + (size_t)14 * (SQ_SCORE_CHUNK + (mode == 0 ? 1 : 0)) * thr;   // (one-pass modes: no carry-over)
-        // mode 0: the structure's strands + skip pointers (10 bytes each) for the longest list a structure of this launch
-        // can have -- device-booked rounds: two strands per stem of the batch's longest stem list; host-driven: 1,024
-        const int str_cap = mode == 0 ? ((chained || pooled) ? std::min(1024, 2 * std::max(b->chain_tmax, 1) + 2) : 1024) : 0;
-        const int str_off = (int)((dyn + 15) & ~(size_t)15);
-        if (mode == 0) dyn = (size_t)str_off + (size_t)10 * str_cap + 16;
+        // behind them the cell table (K R x (K R | 1) doubles for the batch's largest K R) and the list of the bpscore survivors
+        // of a chunk; mode 0: the structure's strands + skip pointers for the longest list a structure of this launch
+        // can have -- device-booked rounds: two strands per stem of the batch's longest stem list; host-driven: SQ_LDS_STRANDS
+        const int str_cap = mode == 0 ? ((chained || pooled) ? std::min(SQ_LDS_STRANDS, 2 * std::max(b->chain_tmax, 1) + 2) : SQ_LDS_STRANDS) : 0;
+        const SqScoreLds lo = sq_score_lds(lds_n, lds_nr, lds_ns, b->cell_entries, thr, mode, str_cap);
+        const void *const score_fn = mode == 0 ? (const void *)sq_score_kernel : (const void *)sq_bps_kernel;
+        if (!sq_dynamic_lds_ok(score_fn, lo.total)) { sq_set_error("the scoring kernel's tables do not fit the LDS"); return -4; }
         if (mode == 0)
-            hipLaunchKernelGGL(sq_score_kernel, dim3(S, parts), dim3(thr), dyn, st, b->ctx, d_structs, d_strands, b->state,
-                               scan, io, lds_n, lds_nr, lds_ns, surv_off, cell_off, str_off, str_cap, ctx_on ? b->ctxtab : SqCtxTab{}, b->score_bound ? 1 : 0);
+            hipLaunchKernelGGL(sq_score_kernel, dim3(S, parts), dim3(thr), lo.total, st, b->ctx, d_structs, d_strands, b->state,
+                               scan, io, lo, ctx_on ? b->ctxtab : SqCtxTab{}, b->score_bound ? 1 : 0);
         else
-            hipLaunchKernelGGL(sq_bps_kernel, dim3(S, parts), dim3(thr), dyn, st, b->ctx, d_structs, d_strands, b->state,
-                               scan, io, mode, lds_n, lds_nr, surv_off, cell_off);
+            hipLaunchKernelGGL(sq_bps_kernel, dim3(S, parts), dim3(thr), lo.total, st, b->ctx, d_structs, d_strands, b->state,
+                               scan, io, mode, lo);
         if (mode == 0 && !chained)
             hipLaunchKernelGGL(sq_select_kernel, dim3(S, std::max(1, parts / 2)), dim3(256), 0, st, b->ctx, d_structs, scan, io);
         if (chained && !pooled) {
             SqChainIO cio = b->chain;
             // dynamic LDS: the level scratch for the longest stem list any job of the batch can reach
             const size_t ext_lds = sq_extend_lds_bytes(b->chain_tmax);
-            if (ext_lds > 64 * 1024) sq_max_dynamic_lds((const void *)sq_chain_kernel, 160 * 1024);
+            if (!sq_dynamic_lds_ok((const void *)sq_chain_kernel, ext_lds)) { sq_set_error("the level scratch of a chained structure does not fit the LDS"); return -4; }
             hipLaunchKernelGGL(sq_chain_kernel, dim3(S), dim3(64), ext_lds, st, b->ctx, d_structs, scan, cio, b->chain_tmax);
         }
         if (pooled) {
-            // survivors within subopt x best the choose kernel sorts in LDS (18 bytes each): 1,024 for long sequences, 384 up to
+            // survivors within subopt x best the choose kernel sorts in LDS (sq_pool_choose_lds): 1,024 for long sequences, 384 up to
             // 200 nt (measured on SRtest150 under nobpp / alt / greedynobpp: at most a few dozen are ever in range)
             const int short_surv = tu.pool_short_nsurv;
             const int nsurv = maxn <= 200 ? short_surv : 1024;
-            hipLaunchKernelGGL(sq_pool_choose_kernel, dim3(S), dim3(64), (size_t)18 * nsurv + 16, st, b->ctx, d_structs, scan, b->pool_io, nsurv);
+            hipLaunchKernelGGL(sq_pool_choose_kernel, dim3(S), dim3(64), sq_pool_choose_lds(nsurv).total, st, b->ctx, d_structs, scan, b->pool_io, nsurv);
         }
     }
+    return 0;
 }
 
 static int run_chunk(sq_batch *b, SqLane &ln, const std::vector<SView> &structs, size_t lo, size_t hi, int mode,
@@ -361,7 +354,7 @@ static int run_chunk(sq_batch *b, SqLane &ln, const std::vector<SView> &structs,
     io.h_ctr = ln.h_ctr; io.h_seq = ln.h_seq;
     SqScanArgs scan = b->scan;                           // this lane's counters
     scan.ctr = ln.d_ctr;
-    sq_launch_round_kernels(b, st, S, maxn, maxcap, need_reacts, scan_bytes, mode, io, scan, ln.d_structs, ln.d_strands, false);
+    if (int r = sq_launch_round_kernels(b, st, S, maxn, maxcap, need_reacts, scan_bytes, mode, io, scan, ln.d_structs, ln.d_strands, false)) return r;
     {
         if (mode == 2 && sink->ent) {
             // sq_entropy_rows: the survivor lists stay where they are; the entropy kernels read them behind the scoring kernel
@@ -503,7 +496,7 @@ int sq_round_annotate_dev(sq_batch *b, const std::vector<int> &jobs, SqAlgoSize 
     io.h_ctr = ln.h_ctr; io.h_seq = ln.h_seq;
     SqScanArgs scan = b->scan;
     scan.ctr = ln.d_ctr;
-    sq_launch_round_kernels(b, st, S, maxn, maxcap, need_reacts, scan_bytes, 2, io, scan, ln.d_structs, ln.d_strands, false);
+    if (int r = sq_launch_round_kernels(b, st, S, maxn, maxcap, need_reacts, scan_bytes, 2, io, scan, ln.d_structs, ln.d_strands, false)) return r;
     hipLaunchKernelGGL(sq_algo_sizes_kernel, dim3(S), dim3(b->inflight > 1 || b->njobs >= 4096 ? 64 : 256), 0, st, b->ctx, ln.d_structs, scan, h_sizes, raw);
     const uint32_t seq = ++*ln.round_seq;
     hipLaunchKernelGGL(sq_done_kernel, dim3(1), dim3(1), 0, st, io, scan, seq);

@@ -179,15 +179,17 @@ extern "C" __global__ __launch_bounds__(SQ_TAIL_THREADS_WIDE) void sq_tail_rank_
 {
     // (one bitmap of the sequence's positions per wave, in the block's DYNAMIC LDS sized for the batch's longest sequence:
     // a static array for 32,768 nt cost every block 16 KB -- 20 bytes do for 150 nt)
-    extern __shared__ __attribute__((aligned(16))) uint32_t s_bits_dyn[];   // [waves of the block][bitwords], then keycap x (3 rank keys, priority)
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_bits_dyn[];   // [waves of the block][bitwords], then sq_tail_rank_lds's other regions
     __shared__ uint32_t s_wsum[SQ_TAIL_THREADS_WIDE / 64];
     __shared__ uint32_t s_run;
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t nthr = blockDim.x, nwv = nthr >> 6;                  // (the entry-per-wave passes b and e are as fast as the block has waves)
-    double *const s_key = reinterpret_cast<double *>(s_bits_dyn + ((nwv * (uint32_t)bitwords + 1u) & ~1u));   // [keycap][3], in rankby order
-    uint8_t *const s_pri = reinterpret_cast<uint8_t *>(s_key + 3 * (size_t)keycap);                          // [keycap]
-    uint8_t *const s_codes = s_pri + (((size_t)keycap + 7) & ~(size_t)7);                                    // [32 x bitwords] the sequence's letter codes
-    int16_t *const s_refp = reinterpret_cast<int16_t *>(s_codes + 32 * (size_t)bitwords);                   // [32 x bitwords] partners in the known structure (refp_lds)
+    const SqTailRankLds lo = sq_tail_rank_lds((int)nwv, bitwords, keycap, refp_lds);
+    char *const dyn = reinterpret_cast<char *>(s_bits_dyn);
+    double *const s_key = reinterpret_cast<double *>(dyn + lo.key);      // [keycap][3], in rankby order
+    uint8_t *const s_pri = reinterpret_cast<uint8_t *>(dyn + lo.pri);    // [keycap]
+    uint8_t *const s_codes = reinterpret_cast<uint8_t *>(dyn + lo.codes);   // [32 x bitwords] the sequence's letter codes
+    int16_t *const s_refp = reinterpret_cast<int16_t *>(dyn + lo.refp);  // [32 x bitwords] partners in the known structure (refp_lds)
     __shared__ int s_nsep;
     SqTailSeq &S = t.seqs[s];
     const uint32_t first = S.first, M = S.count;
@@ -602,9 +604,9 @@ extern "C" __global__ __launch_bounds__(1024) void sq_tail_offsets_kernel(SqTail
 // the header, the scores / masks, the metrics and the consensus row.
 extern "C" __global__ __launch_bounds__(64) void sq_tail_pack_kernel(SqDevCtx c, SqTailIO t, int rowcap, long long rec_cap, long long txt_cap)
 {
-    extern __shared__ __attribute__((aligned(16))) char sq_tail_dyn[];   // [rowcap int16 row][sq_extend_lds_bytes(tmax)]
+    extern __shared__ __attribute__((aligned(16))) char sq_tail_dyn[];   // sq_tail_pack_lds: [rowcap int16 row][sq_extend_lds_bytes(tmax)]
     int16_t *row = reinterpret_cast<int16_t *>(sq_tail_dyn);
-    SqExtendLds L = sq_extend_lds(sq_tail_dyn + (((size_t)rowcap * 2 + 15) & ~(size_t)15), t.tmax);
+    SqExtendLds L = sq_extend_lds(sq_tail_dyn + sq_tail_pack_ext(rowcap), t.tmax);
     const int s = blockIdx.x, y = blockIdx.y, Y = gridDim.y, lane = threadIdx.x;
     const SqTailSeq S = t.seqs[s];
     const SqJob jb = c.jobs[t.seq_job0[s]];
@@ -741,7 +743,7 @@ extern "C" __global__ __launch_bounds__(1024) void sq_tail_pairs_off_kernel(SqDe
 extern "C" __global__ __launch_bounds__(64) void sq_tail_pairs_kernel(SqDevCtx c, SqTailIO t, int32_t *partner, double *scores, unsigned long long *masks,
                                                                       double *metrics, const long long *row_off, const long long *cell_off)
 {
-    extern __shared__ __attribute__((aligned(16))) int32_t sq_pairs_row[];   // [n rounded up to 4]
+    extern __shared__ __attribute__((aligned(16))) int32_t sq_pairs_row[];   // [n rounded up to 4] (sq_tail_pairs_lds)
     int32_t *const row = sq_pairs_row;
     const int s = blockIdx.x, y = blockIdx.y, Y = gridDim.y, lane = threadIdx.x;
     const SqTailSeq S = t.seqs[s];
@@ -952,28 +954,25 @@ int sq_tail_device(sq_batch *b, const sq_fold_opts &o, const int32_t *ref_off, c
         // sequence instead of four -- the per-entry passes of the slowest sequence are what the fold's tail waits for
         const bool wide = !(b->inflight > 1 || b->njobs >= 4096) && b->njobs > b->nseq;
         const int thr = wide ? SQ_TAIL_THREADS_WIDE : SQ_TAIL_THREADS;
-        const int keycap = wide ? 1024 : 256;                    // rank keys staged in LDS (25 bytes each; more structures: global path)
-        const int refp_lds = bitwords <= 128 ? 1 : 0;                // the known structure's partner array in LDS too (sequences up to 4,096 nt)
-        const size_t lds = ((((size_t)(thr / 64) * bitwords + 1) & ~(size_t)1) * 4) + (size_t)keycap * 24 + (((size_t)keycap + 7) & ~(size_t)7) + (size_t)32 * bitwords + 16 +
-                           (refp_lds ? (size_t)64 * bitwords : 0);   // + the letter codes (+ the partners)
-        if (lds > 160 * 1024) return 1;                          // (the host tail takes such a batch)
-        if (lds > 64 * 1024) sq_max_dynamic_lds((const void *)sq_tail_rank_kernel, 160 * 1024);
+        const int keycap = wide ? 1024 : 256;                    // rank keys staged in LDS (three keys and a priority byte each; more structures: global path)
+        const int refp_lds = sq_tail_refp_lds(bitwords);         // the known structure's partner array in LDS too (sequences up to 4,096 nt)
+        const size_t lds = sq_tail_rank_lds(thr / 64, bitwords, keycap, refp_lds).total;
+        if (!sq_dynamic_lds_ok((const void *)sq_tail_rank_kernel, lds)) return 1;   // (the host tail takes such a batch)
         hipLaunchKernelGGL(sq_tail_rank_kernel, dim3(b->nseq), dim3(thr), lds, st, b->ctx, t, bitwords, keycap, refp_lds);
     }
     uint32_t seq = ++*ln.round_seq;
     hipLaunchKernelGGL(sq_tail_offsets_kernel, dim3(1), dim3(1024), 0, st, t, ln.h_seq, seq);
     if (sq_check(hipGetLastError(), "device tail launch")) return 2;
-    const int rowcap = (b->maxn + 8) & ~7;
-    const size_t dyn = (((size_t)rowcap * 2 + 15) & ~(size_t)15) + sq_extend_lds_bytes(t.tmax);
-    if (dyn > 160 * 1024) return 1;
-    if (dyn > 64 * 1024) sq_max_dynamic_lds((const void *)sq_tail_pack_kernel, 160 * 1024);
+    const SqTailPackLds plo = sq_tail_pack_lds(b->maxn, t.tmax);
+    const size_t dyn = plo.total;
+    if (!sq_dynamic_lds_ok((const void *)sq_tail_pack_kernel, dyn)) return 1;
     // The records go straight into pinned buffers.  With buffers of an earlier fold at hand the pack kernel is launched
     // right behind the offsets -- no host round trip in between --, with the shape of that fold; a record that does not fit is
     // reported and the launch repeated with larger buffers.  The first fold of a batch waits for the sizes.
     auto launch_pack = [&](int maxshow) -> uint32_t {
         const int Y = std::max(1, std::min({maxshow, 64, std::max(1, 8192 / std::max(b->nseq, 1))}));
         t.rec_buf = b->h_rec; t.txt_buf = b->h_txt; t.deep = b->h_deep;
-        hipLaunchKernelGGL(sq_tail_pack_kernel, dim3(b->nseq, Y), dim3(64), dyn, st, b->ctx, t, rowcap, (long long)b->h_rec_cap, (long long)b->h_txt_cap);
+        hipLaunchKernelGGL(sq_tail_pack_kernel, dim3(b->nseq, Y), dim3(64), dyn, st, b->ctx, t, plo.rowcap, (long long)b->h_rec_cap, (long long)b->h_txt_cap);
         const uint32_t sq2 = ++*ln.round_seq;
         hipLaunchKernelGGL(sq_tail_done_kernel, dim3(1), dim3(1024), 0, st, t, b->h_rec_off, b->h_txt_off, ln.h_seq, sq2);
         return sq2;
@@ -1034,9 +1033,8 @@ int sq_tail_pairs_launch(sq_batch *b, int32_t *d_partner, double *d_scores, uint
     SqTailIO t = b->tail;
     t.conslim = b->packed_conslim;
     // (coordinates are int16: a row is at most 128 KB and always fits the LDS of a CU)
-    const size_t dyn = (((size_t)b->maxn + 3) & ~(size_t)3) * 4 + 16;
-    if (dyn > 160 * 1024) { sq_set_error("a row of partners does not fit the LDS"); return -1; }
-    if (dyn > 64 * 1024) sq_max_dynamic_lds((const void *)sq_tail_pairs_kernel, 160 * 1024);
+    const size_t dyn = sq_tail_pairs_lds(b->maxn);
+    if (!sq_dynamic_lds_ok((const void *)sq_tail_pairs_kernel, dyn)) { sq_set_error("a row of partners does not fit the LDS"); return -1; }
     static_assert(sizeof(long long) == sizeof(int64_t), "offsets are 64-bit");
     long long *ro = reinterpret_cast<long long *>(d_row_off), *co = reinterpret_cast<long long *>(d_cell_off);
     hipLaunchKernelGGL(sq_tail_pairs_off_kernel, dim3(1), dim3(1024), 0, st, b->ctx, t, ro, co);

@@ -550,6 +550,35 @@ SQ_API int sq_covariation_scan(const uint8_t *d_rows, int32_t R, int32_t L, int3
 SQ_API int sq_covariation_pairs(const uint8_t *d_rows, int32_t R, int32_t L, const int32_t *d_pairs, int64_t P, void *d_scratch,
                                 size_t scratch_bytes, int32_t *d_counts, int64_t *d_cov, uint64_t *d_out, void *hip_stream);
 
+/* ---- covariation statistics of alignment columns (CovariationStatistics) ------------------------------------
+ * d_rows as above.  For columns v < w the joint table n[a * 4 + b] (int32, a, b in A C G U) = the rows with residue a at v
+ * and b at w; rows with a gap or "other" at either column take part in nothing.  N = the sum of n, na / nb its marginals.
+ * statistic 0 / 1 / 2 = mi / gt / chi: S = the sum over n > 0 of (n / N) ln(n N / (na nb)); 2 * the sum over n > 0 of
+ * n ln(n N / (na nb)); the sum over na nb > 0 of (n - e)^2 / e with e = na nb / N.  S = 0 when N = 0 (csrc/sq_covar_stat.h).
+ * correction 0 / 1 / 2 = none / apc / asc, from the means over every pair of distinct columns (no minspan, no threshold):
+ * mean[c] = the sum over c' != c of S(c, c') / (L - 1), mean_all = the mean of S over v < w.  apc: C = S - mean[v] mean[w] /
+ * mean_all (S when mean_all = 0); asc: C = S - (mean[v] + mean[w] - mean_all); none: C = S.  With a correction d_mean
+ * double[L + 1] receives mean[0 .. L - 1] and mean_all at [L], by a first pass over every cell whose sums have a fixed order
+ * (no float atomics: two calls give the same bits); with none d_mean may be null and the pass is skipped.
+ * A record is n[16], S (d_raw) and C (d_value).  d_scratch: sq_covariation_stat_scratch(R, L) bytes, 8-byte aligned (the bit
+ * planes and the first pass's partial column sums, ceil(L / 32) x (L rounded up to 64) doubles).
+ * sq_covariation_stat_scan: every cell with w - v >= minspan, N >= min_rows and C >= min_stat (-infinity: every C) leaves one
+ * record, unordered, d_flat = v * L + w.  d_out[0] = the number of such cells (may exceed cap: then only cap were stored and
+ * nothing is written beyond cap), d_out[1] = 0.
+ * sq_covariation_stat_pairs: the records of the P column pairs d_pairs int32[P * 2] = (v, w), in their order.  d_out[0] = 0,
+ * d_out[1] = 0, or 2 when a pair was not 0 <= v < w < L: that pair's record is all zero, every other record is right.
+ * Asynchronous on hip_stream, allocate nothing; 0, or -1 (a null pointer, R < 1, L < 1, an unknown statistic or correction,
+ * scratch too small, a negative minspan, min_rows, cap or P, a NaN min_stat: nothing enqueued; the record pointers may be
+ * null when cap or P is 0). */
+SQ_API size_t sq_covariation_stat_scratch(int32_t R, int32_t L);
+SQ_API int sq_covariation_stat_scan(const uint8_t *d_rows, int32_t R, int32_t L, int32_t statistic, int32_t correction, int32_t minspan,
+                                    int32_t min_rows, double min_stat, void *d_scratch, size_t scratch_bytes, double *d_mean,
+                                    int64_t *d_flat, int32_t *d_joint, double *d_raw, double *d_value, int64_t cap, uint64_t *d_out,
+                                    void *hip_stream);
+SQ_API int sq_covariation_stat_pairs(const uint8_t *d_rows, int32_t R, int32_t L, int32_t statistic, int32_t correction,
+                                     const int32_t *d_pairs, int64_t P, void *d_scratch, size_t scratch_bytes, double *d_mean,
+                                     int32_t *d_joint, double *d_raw, double *d_value, uint64_t *d_out, void *hip_stream);
+
 /* ---- the shuffled-column null of cov (CovariationSignificance) ---------------------------------------------------------
  * Sample k of K permutes the rows of every column of the alignment on its own: row r of column c gets the key
  * z = seed + 0x9E3779B97F4A7C15 * (1 + ((k * L + c) * R + r)) mod 2^64, the splitmix64 finaliser, (z & ~0xFFFF) | r, and row j

@@ -9,6 +9,7 @@
 // All buffers are the caller's device memory, everything is enqueued on the caller's stream, nothing is allocated or waited for.
 #include "sq_host_int.h"
 #include "sq_covar.h"
+#include "sq_covar_planes.h"
 #include "sq_emit.h"
 
 // One block per 64 rows x 64 columns of the alignment.  The bytes are read row by row, 64 contiguous bytes per wave, and their
@@ -146,9 +147,9 @@ extern "C" size_t sq_covariation_scratch(int32_t R, int32_t L)
     return R < 1 || L < 1 ? 0 : (size_t)SqCovar::plane_words(R, L) * sizeof(uint64_t);
 }
 
-// The checks both entries share, and the planes of the rows in d_scratch.
-static int covar_planes(const char *who, const uint8_t *d_rows, int32_t R, int32_t L, void *d_scratch, size_t scratch_bytes,
-                        uint64_t *d_out, hipStream_t st)
+// The checks both entries share, and the planes of the rows in d_scratch (sq_covar_planes.h: sq_covar_stat_dev.hip calls it too).
+int covar_planes(const char *who, const uint8_t *d_rows, int32_t R, int32_t L, void *d_scratch, size_t scratch_bytes,
+                 uint64_t *d_out, hipStream_t st)
 {
     if (!d_rows || !d_scratch || !d_out || R < 1 || L < 1) {
         sq_set_error(std::string(who) + ": bad argument");

@@ -1,0 +1,308 @@
+// Covariation statistics of alignment columns (CovariationStatistics): MI, the G-test or chi-square of the joint table of every
+// pair of columns, raw and corrected by the column means, on the device.  Definitions, layout and predicates: sq_covar_stat.h.
+//
+//   sq_covar_planes_kernel         (sq_covar_dev.hip) the rows as bit planes; the planes A, C, G, U are read here
+//   sq_covar_stat_sums_kernel      pass 1: S of every cell v < w, tile by tile from LDS, reduced per tile along both axes into
+//                                  partial column sums, one writer per (tile, column)
+//   sq_covar_stat_reduce_kernel    a column's partials in ascending tile order: mean[c]
+//   sq_covar_stat_total_kernel     mean_all from mean[], one block, a fixed order
+//   sq_covar_stat_scan_kernel      pass 2: the counters and S again (cheaper than an L x L store), C, and the cells that pass the
+//                                  thresholds through the block's emission stage (sq_emit.h)
+//   sq_covar_stat_pairs_kernel     the same record for given column pairs, one lane per pair from global memory
+//
+// No float atomics: every sum has one fixed order, so two calls give the same bits.  All buffers are the caller's device
+// memory, everything is enqueued on the caller's stream, nothing is allocated or waited for.
+#include "sq_host_int.h"
+#include "sq_covar_stat.h"
+#include "sq_covar_planes.h"
+#include "sq_emit.h"
+#include <cmath>
+
+namespace {
+
+constexpr int T = SQ_COVSTAT_TILE, CH = SQ_COVSTAT_WORD_CHUNK, CELLS = SQ_COVSTAT_CELLS, PASSES = 4 / CELLS;
+static_assert(T == 32 && SQ_EMIT_BLOCK == 256 && CELLS * PASSES == 4, "a tile is four cells per thread of a 256-thread block");
+
+struct StatPlanesLds {
+    uint64_t v[4][CH][T], w[4][CH][T];                              // the planes A C G U of the tile's two column ranges
+};
+
+// A tile of 32 x 32 cells is walked in PASSES = 4 / CELLS passes of 32 / PASSES rows of cells each; in a pass thread t has
+// the CELLS cells w = w0 + t % 32, v = v0 + vl .. vl + CELLS - 1 with vl = pass * (32 / PASSES) + CELLS * (t / 32), and keeps
+// their 16 counters each in registers (half a wave reads 32 consecutive words of the w planes, and one word of the v planes as a
+// broadcast, as sq_covar_scan_kernel).  CELLS = 2 (sq_covar_stat.h says why): the tile's planes are staged twice.
+// tile_counters() is one pass: per CH words of rows the planes of both column ranges are staged in LDS; words beyond W are
+// staged as zero, so every trip count is block-uniform.  v0 + 31, w0 + 31 < Lpad (a multiple of 64 >= L).
+__device__ __forceinline__ void tile_counters(const uint64_t *plane, int64_t W, int64_t Lpad, int64_t v0, int64_t w0, StatPlanesLds &s,
+                                              int vl, int32_t cnt[CELLS][16])
+{
+    const int tid = threadIdx.x, wl = tid & 31;
+    for (int64_t wb = 0; wb < W; wb += CH) {
+        __syncthreads();                                             // (the last chunk has been read)
+        for (int i = tid; i < 4 * CH * T; i += 256) {
+            const int p = i / (CH * T), wd = i / T % CH, col = i % T;
+            const bool have = wb + wd < W;
+            s.v[p][wd][col] = have ? plane[SqCovar::at(p, wb + wd, v0 + col, W, Lpad)] : 0ull;
+            s.w[p][wd][col] = have ? plane[SqCovar::at(p, wb + wd, w0 + col, W, Lpad)] : 0ull;
+        }
+        __syncthreads();
+        for (int wd = 0; wd < CH; wd++) {
+            uint64_t b[4];
+            for (int p = 0; p < 4; p++) b[p] = s.w[p][wd][wl];
+#pragma unroll
+            for (int c = 0; c < CELLS; c++) {
+                uint64_t a[4];
+                for (int p = 0; p < 4; p++) a[p] = s.v[p][wd][vl + c];
+                SqCovarStat::accumulate(a, b, cnt[c]);
+            }
+        }
+    }
+}
+
+// The 16 counters of one cell from global memory (the pairs lookup, and the scan's flush for the records it writes).
+__device__ __forceinline__ void cell_counters(const uint64_t *plane, int64_t W, int64_t Lpad, int64_t v, int64_t w, int32_t n[16])
+{
+    for (int k = 0; k < 16; k++) n[k] = 0;
+    for (int64_t wd = 0; wd < W; wd++) {
+        uint64_t a[4], b[4];
+        for (int p = 0; p < 4; p++) {
+            a[p] = plane[SqCovar::at(p, wd, v, W, Lpad)];
+            b[p] = plane[SqCovar::at(p, wd, w, W, Lpad)];
+        }
+        SqCovarStat::accumulate(a, b, n);
+    }
+}
+
+}  // namespace
+
+// Pass 1.  A block takes the upper-triangle tiles k = blockIdx.x, + gridDim.x, ... (SqCovar::tile_of).  S of the tile's cells
+// v < w < L (0.0 elsewhere) goes to LDS; then thread t < 32 adds row t of the tile over w ascending (what the tile gives to
+// sum[v0 + t]) and thread 32 + t column t over v ascending (to sum[w0 + t]).  Tile (ti, tj) writes the row sums to
+// partial[tj][v0 + t] and the column sums to partial[ti][w0 + t]; the diagonal tile writes row + column to partial[ti][v0 + t].
+// So slot (t, c) of partial[nT][Lpad], c < nT * 32 <= Lpad, has exactly one writer, the tile that column c's range shares with
+// range t, and every such slot is written: nothing is cleared beforehand.
+extern "C" __global__ __launch_bounds__(256) void sq_covar_stat_sums_kernel(const uint64_t *plane, int32_t R, int32_t L, int32_t stat,
+                                                                           double *partial)
+{
+    __shared__ StatPlanesLds s_pl;
+    __shared__ double s_S[T][T + 1], s_row[T], s_col[T];
+    const int tid = threadIdx.x, wl = tid & 31;
+    const int64_t W = SqCovar::words(R), Lpad = SqCovar::lpad(L);
+    const int64_t nT = SqCovarStat::tiles(L), ntiles = SqCovar::tile_count(nT);
+    for (int64_t k = blockIdx.x; k < ntiles; k += gridDim.x) {
+        int32_t ti, tj;
+        SqCovar::tile_of(k, nT, ti, tj);
+        const int64_t v0 = (int64_t)ti * T, w0 = (int64_t)tj * T;
+        for (int pass = 0; pass < PASSES; pass++) {
+            const int vl = pass * (T / PASSES) + (tid >> 5) * CELLS;
+            int32_t cnt[CELLS][16] = {};
+            tile_counters(plane, W, Lpad, v0, w0, s_pl, vl, cnt);
+#pragma unroll
+            for (int c = 0; c < CELLS; c++) {
+                const int64_t v = v0 + vl + c, w = w0 + wl;
+                s_S[vl + c][wl] = v < w && w < L ? SqCovarStat::raw(stat, cnt[c]) : 0.0;
+            }
+        }
+        __syncthreads();
+        if (tid < 2 * T) {
+            const int t = tid & (T - 1);
+            double sum = 0.0;
+            if (tid < T) for (int j = 0; j < T; j++) sum += s_S[t][j];
+            else for (int j = 0; j < T; j++) sum += s_S[j][t];
+            (tid < T ? s_row : s_col)[t] = sum;
+        }
+        __syncthreads();
+        if (tid < T) {
+            if (ti == tj) partial[(int64_t)ti * Lpad + v0 + tid] = s_row[tid] + s_col[tid];
+            else {
+                partial[(int64_t)tj * Lpad + v0 + tid] = s_row[tid];
+                partial[(int64_t)ti * Lpad + w0 + tid] = s_col[tid];
+            }
+        }
+        // (the next tile's first barrier, in tile_counters, comes before anything of s_S, s_row or s_col is written again)
+    }
+}
+
+// mean[c] = (the partials of column c in ascending tile order) / (L - 1), one thread per column c < L; 0 with L == 1.
+extern "C" __global__ __launch_bounds__(256) void sq_covar_stat_reduce_kernel(const double *partial, int32_t L, double *mean)
+{
+    const int64_t Lpad = SqCovar::lpad(L), nT = SqCovarStat::tiles(L);
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= L) return;
+    double sum = 0.0;
+    for (int64_t t = 0; t < nT; t++) sum += partial[t * Lpad + c];
+    mean[c] = L > 1 ? sum / (double)(L - 1) : 0.0;
+}
+
+// mean[L] = mean_all = (the sum of mean[c]) / L: one block; thread t adds the columns t, t + 256, ... ascending, thread 0 the
+// 256 runs ascending.
+extern "C" __global__ __launch_bounds__(256) void sq_covar_stat_total_kernel(int32_t L, double *mean)
+{
+    __shared__ double s_run[256];
+    double sum = 0.0;
+    for (int64_t c = threadIdx.x; c < L; c += 256) sum += mean[c];
+    s_run[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double all = 0.0;
+        for (int t = 0; t < 256; t++) all += s_run[t];
+        mean[L] = all / (double)L;
+    }
+}
+
+// Pass 2: the same tile walk and the same counters.  A cell in scope (v < w < L, w - v >= minspan) with N >= min_rows gets
+// S and C; one that also has C >= min_stat is a hit.  The stage keeps a hit's flat index and S (16 bytes; with the 64 bytes
+// of counters a stage of SQ_EMIT_STAGE records would be 72 KB and admit one block per CU); the flush forms the counters of the
+// records it stores again from global memory (cell_counters: integers, the same numbers) and C again from S and the means (the same function
+// of the same numbers: the same bits).  mean = null with corr == SQ_COVSTAT_NONE.  One slot() + step() per cell index of the
+// thread (sq_emit.h's contract: at most 256 records a step).
+extern "C" __global__ __launch_bounds__(256) void sq_covar_stat_scan_kernel(const uint64_t *plane, int32_t R, int32_t L, int32_t stat,
+                                                                           int32_t corr, int32_t minspan, int32_t min_rows, double min_stat,
+                                                                           const double *mean, long long *flat_out, int32_t *joint_out,
+                                                                           double *raw_out, double *value_out, long long cap,
+                                                                           unsigned long long *out)
+{
+    __shared__ StatPlanesLds s_pl;
+    __shared__ long long s_flat[SQ_EMIT_STAGE];
+    __shared__ double s_raw[SQ_EMIT_STAGE];
+    __shared__ SqEmitStage em;
+    const int tid = threadIdx.x, wl = tid & 31;
+    const int64_t W = SqCovar::words(R), Lpad = SqCovar::lpad(L);
+    const int64_t nT = SqCovarStat::tiles(L), ntiles = SqCovar::tile_count(nT);
+    const double mean_all = corr != SQ_COVSTAT_NONE ? mean[L] : 0.0;
+    em.init();
+    auto write = [&](uint32_t k, unsigned long long at) {
+        if ((long long)at < cap) {
+            const long long flat = s_flat[k];
+            const int64_t v = flat / L, w = flat % L;                // (a staged cell: v < w < L)
+            int32_t n[16];
+            cell_counters(plane, W, Lpad, v, w, n);
+            flat_out[at] = flat;
+            for (int j = 0; j < 16; j++) joint_out[at * 16 + j] = n[j];
+            raw_out[at] = s_raw[k];
+            value_out[at] = corr != SQ_COVSTAT_NONE ? SqCovarStat::corrected(corr, s_raw[k], mean[v], mean[w], mean_all) : s_raw[k];
+        }
+    };
+    for (int64_t k = blockIdx.x; k < ntiles; k += gridDim.x) {
+        int32_t ti, tj;
+        SqCovar::tile_of(k, nT, ti, tj);
+        const int64_t v0 = (int64_t)ti * T, w0 = (int64_t)tj * T;
+        for (int pass = 0; pass < PASSES; pass++) {
+            const int vl = pass * (T / PASSES) + (tid >> 5) * CELLS;
+            int32_t cnt[CELLS][16] = {};
+            tile_counters(plane, W, Lpad, v0, w0, s_pl, vl, cnt);
+#pragma unroll
+            for (int c = 0; c < CELLS; c++) {
+                const int64_t v = v0 + vl + c, w = w0 + wl;
+                const int64_t N = SqCovarStat::rows(cnt[c]);
+                bool hit = SqCovar::in_scope(v, w, L, minspan) && N >= min_rows;     // (else no S: the logarithms are the cost)
+                double S = 0.0;
+                if (hit) {
+                    S = SqCovarStat::raw(stat, cnt[c]);
+                    const double C = corr != SQ_COVSTAT_NONE ? SqCovarStat::corrected(corr, S, mean[v], mean[w], mean_all) : S;
+                    hit = SqCovarStat::emits(N, C, min_rows, min_stat);
+                }
+                const uint32_t at = em.slot(hit);
+                if (hit) {
+                    s_flat[at] = (long long)(v * L + w);
+                    s_raw[at] = S;
+                }
+                em.step(out, write);
+            }
+        }
+    }
+    em.finish(out, write);
+}
+
+// Given pairs: one lane per pair, the planes' words read from global memory.  A pair that is not v < w inside the L columns
+// gets an all-zero record and status 2.
+extern "C" __global__ __launch_bounds__(256) void sq_covar_stat_pairs_kernel(const uint64_t *plane, int32_t R, int32_t L, int32_t stat,
+                                                                            int32_t corr, const double *mean, const int32_t *pairs,
+                                                                            long long P, int32_t *joint_out, double *raw_out,
+                                                                            double *value_out, unsigned long long *out)
+{
+    const int64_t W = SqCovar::words(R), Lpad = SqCovar::lpad(L);
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < P; k += (int64_t)gridDim.x * 256) {
+        const int32_t v = pairs[2 * k], w = pairs[2 * k + 1];
+        int32_t n[16] = {};
+        double S = 0.0, C = 0.0;
+        if (!SqCovar::valid_pair(v, w, L)) out[1] = 2ull;
+        else {
+            cell_counters(plane, W, Lpad, v, w, n);
+            S = SqCovarStat::raw(stat, n);
+            C = corr != SQ_COVSTAT_NONE ? SqCovarStat::corrected(corr, S, mean[v], mean[w], mean[L]) : S;
+        }
+        for (int j = 0; j < 16; j++) joint_out[k * 16 + j] = n[j];
+        raw_out[k] = S;
+        value_out[k] = C;
+    }
+}
+
+extern "C" size_t sq_covariation_stat_scratch(int32_t R, int32_t L)
+{
+    return R < 1 || L < 1 ? 0 : (size_t)SqCovarStat::scratch_words(R, L) * 8;
+}
+
+// The checks both entries share; then the planes in d_scratch and, with a correction, pass 1 and the two reductions: d_mean.
+static int stat_open(const char *who, const uint8_t *d_rows, int32_t R, int32_t L, int32_t stat, int32_t corr, void *d_scratch,
+                     size_t scratch_bytes, double *d_mean, uint64_t *d_out, hipStream_t st)
+{
+    if (stat < 0 || stat >= SQ_COVSTAT_STATS || corr < 0 || corr >= SQ_COVSTAT_CORRECTIONS || (corr != SQ_COVSTAT_NONE && !d_mean)) {
+        sq_set_error(std::string(who) + ": bad argument");
+        return -1;
+    }
+    if (R >= 1 && L >= 1 && scratch_bytes < sq_covariation_stat_scratch(R, L)) {
+        sq_set_error(std::string(who) + ": scratch too small");
+        return -1;
+    }
+    if (int rc = covar_planes(who, d_rows, R, L, d_scratch, scratch_bytes, d_out, st)) return rc;
+    if (corr == SQ_COVSTAT_NONE) return 0;
+    const uint64_t *plane = (const uint64_t *)d_scratch;
+    double *partial = (double *)d_scratch + SqCovar::plane_words(R, L);
+    const unsigned blocks = (unsigned)std::min<int64_t>(SqCovar::tile_count(SqCovarStat::tiles(L)), SQ_COVSTAT_MAX_BLOCKS);
+    hipLaunchKernelGGL(sq_covar_stat_sums_kernel, dim3(blocks), dim3(256), 0, st, plane, R, L, stat, partial);
+    if (int rc = sq_check(hipGetLastError(), "sq_covar_stat_sums_kernel")) return rc;
+    hipLaunchKernelGGL(sq_covar_stat_reduce_kernel, dim3((unsigned)(((int64_t)L + 255) / 256)), dim3(256), 0, st, (const double *)partial, L,
+                       d_mean);
+    if (int rc = sq_check(hipGetLastError(), "sq_covar_stat_reduce_kernel")) return rc;
+    hipLaunchKernelGGL(sq_covar_stat_total_kernel, dim3(1), dim3(256), 0, st, L, d_mean);
+    return sq_check(hipGetLastError(), "sq_covar_stat_total_kernel");
+}
+
+extern "C" int sq_covariation_stat_scan(const uint8_t *d_rows, int32_t R, int32_t L, int32_t statistic, int32_t correction, int32_t minspan,
+                                        int32_t min_rows, double min_stat, void *d_scratch, size_t scratch_bytes, double *d_mean,
+                                        int64_t *d_flat, int32_t *d_joint, double *d_raw, double *d_value, int64_t cap, uint64_t *d_out,
+                                        void *hip_stream)
+{
+    if (minspan < 0 || min_rows < 0 || std::isnan(min_stat) || cap < 0 || (cap && (!d_flat || !d_joint || !d_raw || !d_value))) {
+        sq_set_error("sq_covariation_stat_scan: bad argument");
+        return -1;
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = stat_open("sq_covariation_stat_scan", d_rows, R, L, statistic, correction, d_scratch, scratch_bytes, d_mean, d_out, st))
+        return rc;
+    // At most SQ_COVSTAT_MAX_BLOCKS blocks, the rest by grid stride, as sq_covariation_scan.
+    const unsigned blocks = (unsigned)std::min<int64_t>(SqCovar::tile_count(SqCovarStat::tiles(L)), SQ_COVSTAT_MAX_BLOCKS);
+    hipLaunchKernelGGL(sq_covar_stat_scan_kernel, dim3(blocks), dim3(256), 0, st, (const uint64_t *)d_scratch, R, L, statistic, correction,
+                       minspan, min_rows, min_stat, (const double *)d_mean, (long long *)d_flat, d_joint, d_raw, d_value, (long long)cap,
+                       (unsigned long long *)d_out);
+    return sq_check(hipGetLastError(), "sq_covar_stat_scan_kernel");
+}
+
+extern "C" int sq_covariation_stat_pairs(const uint8_t *d_rows, int32_t R, int32_t L, int32_t statistic, int32_t correction,
+                                         const int32_t *d_pairs, int64_t P, void *d_scratch, size_t scratch_bytes, double *d_mean,
+                                         int32_t *d_joint, double *d_raw, double *d_value, uint64_t *d_out, void *hip_stream)
+{
+    if (P < 0 || (P && (!d_pairs || !d_joint || !d_raw || !d_value))) {
+        sq_set_error("sq_covariation_stat_pairs: bad argument");
+        return -1;
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = stat_open("sq_covariation_stat_pairs", d_rows, R, L, statistic, correction, d_scratch, scratch_bytes, d_mean, d_out, st))
+        return rc;
+    if (!P) return 0;
+    const unsigned blocks = (unsigned)std::min<int64_t>((P + 255) / 256, SQ_COVSTAT_MAX_BLOCKS);
+    hipLaunchKernelGGL(sq_covar_stat_pairs_kernel, dim3(blocks), dim3(256), 0, st, (const uint64_t *)d_scratch, R, L, statistic, correction,
+                       (const double *)d_mean, d_pairs, (long long)P, d_joint, d_raw, d_value, (unsigned long long *)d_out);
+    return sq_check(hipGetLastError(), "sq_covar_stat_pairs_kernel");
+}

@@ -18,6 +18,14 @@ DUPLEX_SUMMARY_MAX_BLOCKS = 2048
 COVAR_TILE = 32
 COVAR_WORD_CHUNK = 4
 COVAR_MAX_BLOCKS = 2048
+#: sq_covariation_stat_scan's tile of columns, the 64-row words it keeps in LDS at a time and the most blocks it launches
+#: (SQ_COVSTAT_TILE, SQ_COVSTAT_WORD_CHUNK, SQ_COVSTAT_MAX_BLOCKS, csrc/sq_covar_stat.h)
+COVAR_STAT_TILE = 32
+COVAR_STAT_WORD_CHUNK = 4
+COVAR_STAT_MAX_BLOCKS = 2048
+#: the statistics and the corrections of sq_covariation_stat_scan / _pairs by name (SQ_COVSTAT_*, csrc/sq_covar_stat.h)
+COVAR_STATISTICS = ("mi", "gt", "chi")
+COVAR_CORRECTIONS = (None, "apc", "asc")
 #: the most rows sq_covariation_null shuffles on the device and the bins its scan keeps in LDS (SQ_COVNULL_MAX_ROWS,
 #: SQ_COVNULL_LDS_BINS, csrc/sq_covar_null.h)
 COVAR_NULL_MAX_ROWS = 4096
@@ -295,6 +303,62 @@ class DeviceCalls:
                                               _ptr(counts if P else None), _ptr(cov if P else None), _ptr(out), _stream(dev)))
             _result_words(out, "sq_covariation_pairs: a pair is not 0 <= v < w < %d columns" % Lcols)
         return counts, cov
+
+    def _covariation_stat_buffers(self, rows, statistic, correction):
+        """What covariation_stat_scan and covariation_stat_pairs share: (stat, corr, scratch, its bytes, mean or None)."""
+        import torch
+        L = _lib.load()
+        assert rows.dtype == torch.uint8 and rows.is_cuda and rows.dim() == 2 and rows.is_contiguous()
+        stat, corr = COVAR_STATISTICS.index(statistic), COVAR_CORRECTIONS.index(correction)
+        R, Lcols = int(rows.shape[0]), int(rows.shape[1])
+        nbytes = int(L.sq_covariation_stat_scratch(R, Lcols))
+        scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=rows.device)
+        mean = torch.empty(Lcols + 1, dtype=torch.float64, device=rows.device) if corr else None
+        return stat, corr, scratch, nbytes, mean
+
+    def covariation_stat_scan(self, rows, statistic="gt", correction="apc", minspan=4, min_rows=1, min_stat=None, cap=None):
+        """Covariation statistics of every pair of columns of an alignment, on the device (sq_covariation_stat_scan): rows = uint8
+        device tensor [R, L] of the rows' ASCII bytes, statistic one of COVAR_STATISTICS, correction one of COVAR_CORRECTIONS.
+        Returns the device tensors (flat int64 = v * L + w, joint int32[P, 16] = the rows with residue a at v and b at w at
+        [a * 4 + b], a and b in A C G U, raw float64[P] = S, value float64[P] = the corrected C, mean float64[L + 1] = the
+        column means of S and, last, the mean of all cells; None without a correction) of the cells with w - v >= minspan, at
+        least min_rows rows in the table and C >= min_stat (None: every C), unordered.  `cap` (default 1 << 16) sizes the result
+        buffers; the call is repeated with the true number when it was too small (matrix_select's protocol).  Only that
+        number comes to the host."""
+        import torch
+        L = _lib.load()
+        dev, R, Lcols = rows.device, int(rows.shape[0]), int(rows.shape[1])
+        cap = 1 << 16 if cap is None else int(cap)
+        floor = float("-inf") if min_stat is None else float(min_stat)
+
+        def call(res, cap, out):                                   # (the entry has no status: out[1] stays 0)
+            _lib.check(L.sq_covariation_stat_scan(_ptr(rows), R, Lcols, stat, corr, int(minspan), int(min_rows), floor, _ptr(scratch), nbytes,
+                                                  _ptr(mean), _ptr(res[0]), _ptr(res[1]), _ptr(res[2]), _ptr(res[3]), cap, _ptr(out),
+                                                  _stream(dev)))
+
+        with torch.cuda.device(dev):
+            stat, corr, scratch, nbytes, mean = self._covariation_stat_buffers(rows, statistic, correction)
+            return _call_until_fits(dev, cap, (torch.int64, (torch.int32, 16), torch.float64, torch.float64), call, None) + (mean,)
+
+    def covariation_stat_pairs(self, rows, pairs, statistic="gt", correction="apc"):
+        """The same numbers for given column pairs (sq_covariation_stat_pairs): pairs = int32 device tensor [P, 2] of (v, w),
+        0 <= v < w < L.  Returns the device tensors (joint int32[P, 16], raw float64[P], value float64[P], mean float64[L + 1] or
+        None) in the pairs' order; RuntimeError when a pair is not such a pair.  Only the two result words come to the host."""
+        import torch
+        L = _lib.load()
+        assert pairs.dtype == torch.int32 and pairs.dim() == 2 and int(pairs.shape[1]) == 2 and pairs.device == rows.device
+        dev, R, Lcols, P = rows.device, int(rows.shape[0]), int(rows.shape[1]), int(pairs.shape[0])
+        pairs = pairs.contiguous()
+        with torch.cuda.device(dev):
+            stat, corr, scratch, nbytes, mean = self._covariation_stat_buffers(rows, statistic, correction)
+            joint = torch.empty((P, 16), dtype=torch.int32, device=dev)
+            raw, value = torch.empty(P, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.float64, device=dev)
+            out = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.check(L.sq_covariation_stat_pairs(_ptr(rows), R, Lcols, stat, corr, _ptr(pairs if P else None), P, _ptr(scratch), nbytes,
+                                                   _ptr(mean), _ptr(joint if P else None), _ptr(raw if P else None),
+                                                   _ptr(value if P else None), _ptr(out), _stream(dev)))
+            _result_words(out, "sq_covariation_stat_pairs: a pair is not 0 <= v < w < %d columns" % Lcols)
+        return joint, raw, value, mean
 
     def covariation_null_planes(self, rows, k, seed, count=None):
         """The bit planes of sample k of the shuffled-column null of an alignment (sq_covariation_null_planes): rows = uint8

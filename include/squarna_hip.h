@@ -604,6 +604,29 @@ SQ_API int sq_covariation_null(const uint8_t *d_rows, int32_t R, int32_t L, int3
 SQ_API int sq_covariation_null_planes(const uint8_t *d_rows, int32_t R, int32_t L, int64_t k, int32_t count, uint64_t seed,
                                       void *d_scratch, size_t scratch_bytes, void *hip_stream);
 
+/* ---- the shuffled-column null of the covariation statistics (CovariationStatisticsSignificance) ------------------------
+ * The shuffle of sq_covariation_null and the statistics of sq_covariation_stat_scan (statistic 0 / 1 / 2 = mi / gt / chi,
+ * correction 0 / 1 / 2 = none / apc / asc): the value of a null cell v < w < L, w - v >= minspan, of sample k is C with
+ * the column means of that shuffled sample over every pair of its distinct columns -- the bits sq_covariation_stat_scan gives
+ * for the shuffled alignment (csrc/sq_covar_stat_null.h).
+ * sq_covariation_stat_null: d_pairs int32[P * 2] and d_value double[P] are the observed pairs and their C, d_thresholds
+ * double[U] sorted distinct values without a NaN (for CovariationStatisticsSignificance those of d_value).  Outputs: d_hist
+ * int64[U + 1], d_hist[b] = the null cells of all K samples with exactly b thresholds <= their C (IEEE comparisons);
+ * d_own_ge int32[P], the samples in which the cell of pair p has C >= d_value[p]; d_null_max double[K], the largest C of a
+ * sample's cells (-infinity without a cell; folded through an integer key, no float atomics: two calls give the same
+ * bits).  d_out[0] = 0, d_out[1] = 0, or 2 when a pair was not 0 <= v < w < L (it counts nothing).  The samples are formed
+ * `batch` at a time in d_scratch (sq_covariation_stat_null_scratch(R, L, batch) bytes, 8-byte aligned: per sample of a batch
+ * the bit planes, the first pass's partial column sums and L + 1 means, then the class bytes of the rows); the results do
+ * not depend on batch.
+ * Asynchronous on hip_stream, allocate nothing; 0, or -1 (a null pointer, R < 1, L < 1, K < 1, an unknown statistic or
+ * correction, batch outside 1..65535, a negative minspan, P or U, R above SQ_COVNULL_MAX_ROWS = 4096, L above 2^21, scratch
+ * too small: nothing enqueued; the pair pointers may be null when P is 0, d_thresholds when U is 0). */
+SQ_API size_t sq_covariation_stat_null_scratch(int32_t R, int32_t L, int32_t batch);
+SQ_API int sq_covariation_stat_null(const uint8_t *d_rows, int32_t R, int32_t L, int32_t statistic, int32_t correction, int32_t minspan,
+                                    const int32_t *d_pairs, const double *d_value, int64_t P, const double *d_thresholds, int64_t U,
+                                    int32_t K, uint64_t seed, int32_t batch, void *d_scratch, size_t scratch_bytes, int64_t *d_hist,
+                                    int32_t *d_own_ge, double *d_null_max, uint64_t *d_out, void *hip_stream);
+
 /* ---- row identities, neighbour counts and the redundancy filter of an alignment (RowIdentity) ----------------------------
  * d_rows uint8[R * L] as for the covariation entries, the bytes classified in the same way; a residue is any non-gap, a base
  * is A, C, G or U, and "other" matches nothing.  For rows a, b: same[a, b] = the columns where both hold the same base,

@@ -223,14 +223,15 @@ static int null_check(const char *who, const void *d_rows, int32_t R, int32_t L,
     return 0;
 }
 
-static int null_classes(const uint8_t *d_rows, int32_t R, int32_t L, uint8_t *d_cls, hipStream_t st)
+// (sq_internal.h declares null_classes and null_planes: sq_covar_stat_dev.hip shuffles with them too)
+int null_classes(const uint8_t *d_rows, int32_t R, int32_t L, uint8_t *d_cls, hipStream_t st)
 {
     const int64_t blocks = (((int64_t)L + 63) / 64) * (((int64_t)R + 63) / 64);      // (<= 2^15 * 2^6)
     hipLaunchKernelGGL(sq_covar_null_classes_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_rows, R, L, d_cls);
     return sq_check(hipGetLastError(), "sq_covar_null_classes_kernel");
 }
 
-static int null_planes(const uint8_t *d_cls, int32_t R, int32_t L, uint64_t seed, uint64_t k0, int32_t samples, uint64_t *d_plane, hipStream_t st)
+int null_planes(const uint8_t *d_cls, int32_t R, int32_t L, uint64_t seed, uint64_t k0, int32_t samples, uint64_t *d_plane, hipStream_t st)
 {
     const size_t lds = (size_t)SqCovarNull::padded(R) * sizeof(uint64_t) + (((size_t)R + 7) & ~(size_t)7);
     hipLaunchKernelGGL(sq_covar_null_planes_kernel, dim3((unsigned)(samples * SqCovar::lpad(L))), dim3(256), lds, st, d_cls, R, L,

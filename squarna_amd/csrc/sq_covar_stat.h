@@ -37,7 +37,9 @@
 // 4 / CELLS passes that each stage the planes again).  The compiler's figures for gfx950, pass 1 / pass 2: with 4 cells 204 /
 // 204 VGPRs, two waves per SIMD; with 2 cells 142 / 152 VGPRs, three waves per SIMD.  S of one cell alone (16 unrolled
 // logarithms on 16 counters) takes 90 VGPRs in the pairs kernel, so a third cell's 16 counters would already cost the third
-// wave.  LDS does not bind: 17 KB (pass 1) and 24 KB (pass 2) a block.
+// wave.  LDS does not bind: 17 KB (pass 1) and 24 KB (pass 2) a block.  The null's scan (sq_covar_stat_null_scan_kernel,
+// sq_covar_stat_null.h) keeps the shape: with 2 cells 160 VGPRs, three waves per SIMD, and 32 KB of LDS a block (the planes,
+// 2048 thresholds and 2048 bins), three blocks in a CU's 160 KB; its pairs kernel takes 94 VGPRs.
 #define SQ_COVSTAT_TILE 32
 #define SQ_COVSTAT_WORD_CHUNK 4
 #define SQ_COVSTAT_MAX_BLOCKS 2048

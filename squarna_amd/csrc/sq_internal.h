@@ -167,3 +167,10 @@ struct SqCounters {
     uint32_t out_ovf;     // out list overflowed
     uint32_t level_ovf;   // a level above SQ_MAXLEVELS was seen
 };
+
+// The shuffled-column null's two host launchers (sq_covar_null_dev.hip), for the entries that shuffle: the class bytes of the
+// rows column after column into d_cls (R * L bytes), and the bit planes of the samples k0 .. k0 + samples - 1 of the shuffled
+// alignments into d_plane (SqCovar::plane_words(R, L) words each), enqueued on st.  The caller has checked R, L and samples
+// (sq_covar_null.h: SQ_COVNULL_MAX_ROWS, SQ_COVNULL_MAX_COLS, samples * lpad(L) < 2^31).
+int null_classes(const uint8_t *d_rows, int32_t R, int32_t L, uint8_t *d_cls, hipStream_t st);
+int null_planes(const uint8_t *d_cls, int32_t R, int32_t L, uint64_t seed, uint64_t k0, int32_t samples, uint64_t *d_plane, hipStream_t st);

@@ -33,6 +33,8 @@ COVAR_NULL_LDS_BINS = 4096
 #: the bytes of shuffled planes covariation_null keeps at a time unless told a batch, and the most samples of a batch
 COVAR_NULL_BATCH_BYTES = 256 << 20
 COVAR_NULL_BATCH = 64
+#: the thresholds and bins sq_covariation_stat_null's scan keeps in LDS (SQ_COVSTATNULL_LDS_BINS, csrc/sq_covar_stat_null.h)
+COVAR_STAT_NULL_LDS_BINS = 2048
 #: sq_row_identity's tile of rows, the 64-column words it keeps in LDS at a time, the most blocks it launches, the most rows
 #: and columns it takes and the words of neighbour bits a lane of its filter kernel holds ahead (SQ_ID_TILE, SQ_ID_WORD_CHUNK, SQ_ID_MAX_BLOCKS,
 #: SQ_ID_MAX_ROWS, SQ_ID_MAX_COLS, SQ_ID_FILTER_WORDS, csrc/sq_identity.h)
@@ -412,6 +414,46 @@ class DeviceCalls:
             # from t + 1 on
             from_bin = torch.flip(torch.cumsum(torch.flip(hist, (0,)), 0), (0,))
             null_ge = from_bin[torch.searchsorted(thresholds, cov) + 1] if P else torch.empty(0, dtype=torch.int64, device=dev)
+        return null_ge, own_ge, null_max
+
+    def covariation_stat_null(self, rows, pairs, value, statistic="gt", correction="apc", minspan=4, samples=100, seed=0, batch=None):
+        """The shuffled-column null of a covariation statistic for observed pairs (sq_covariation_stat_null): rows = uint8 device
+        tensor [R, L], pairs = int32 device tensor [P, 2], value = float64 device tensor [P] (their observed C, no NaN),
+        statistic one of COVAR_STATISTICS, correction one of COVAR_CORRECTIONS.  Returns the device tensors (null_ge int64[P] =
+        the null cells of all samples with C >= value[p], own_ge int32[P] = the samples in which the same cell reaches value[p],
+        null_max float64[samples], -inf for a sample without a cell in scope).  `batch` samples are formed at a time (default: as
+        many as COVAR_NULL_BATCH_BYTES of planes and partial column sums hold, at most COVAR_NULL_BATCH); the results do not
+        depend on it.  RuntimeError when a pair is not 0 <= v < w < L.  Only the two result words come to the host."""
+        import torch
+        L = _lib.load()
+        assert rows.dtype == torch.uint8 and rows.is_cuda and rows.dim() == 2 and rows.is_contiguous()
+        assert pairs.dtype == torch.int32 and pairs.dim() == 2 and int(pairs.shape[1]) == 2 and pairs.device == rows.device
+        assert value.dtype == torch.float64 and value.dim() == 1 and value.device == rows.device and int(value.numel()) == int(pairs.shape[0])
+        stat, corr = COVAR_STATISTICS.index(statistic), COVAR_CORRECTIONS.index(correction)
+        dev, R, Lcols, P, K = rows.device, int(rows.shape[0]), int(rows.shape[1]), int(pairs.shape[0]), int(samples)
+        pairs, value = pairs.contiguous(), value.contiguous()
+        if batch is None:
+            per = int(L.sq_covariation_stat_null_scratch(R, Lcols, 2)) - int(L.sq_covariation_stat_null_scratch(R, Lcols, 1))
+            batch = max(1, min(K, COVAR_NULL_BATCH, COVAR_NULL_BATCH_BYTES // max(per, 1)))
+        batch = int(batch)
+        with torch.cuda.device(dev):
+            thresholds = torch.unique(value)                         # (sorted; -0.0 and 0.0 are one value)
+            U = int(thresholds.numel())
+            nbytes = int(L.sq_covariation_stat_null_scratch(R, Lcols, batch))
+            scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+            hist = torch.empty(U + 1, dtype=torch.int64, device=dev)
+            own_ge = torch.empty(P, dtype=torch.int32, device=dev)
+            null_max = torch.empty(K, dtype=torch.float64, device=dev)
+            out = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.check(L.sq_covariation_stat_null(_ptr(rows), R, Lcols, stat, corr, int(minspan), _ptr(pairs if P else None),
+                                                  _ptr(value if P else None), P, _ptr(thresholds if U else None), U, K, int(seed), batch,
+                                                  _ptr(scratch), nbytes, _ptr(hist), _ptr(own_ge if P else None), _ptr(null_max), _ptr(out),
+                                                  _stream(dev)))
+            _result_words(out, "sq_covariation_stat_null: a pair is not 0 <= v < w < %d columns" % Lcols)
+            # hist[b] = the null cells with exactly b thresholds <= their C: value[p], the t-th threshold, is reached by the bins
+            # from t + 1 on
+            from_bin = torch.flip(torch.cumsum(torch.flip(hist, (0,)), 0), (0,))
+            null_ge = from_bin[torch.searchsorted(thresholds, value) + 1] if P else torch.empty(0, dtype=torch.int64, device=dev)
         return null_ge, own_ge, null_max
 
     def row_identity(self, rows, denominator=0, threshold_bp=8000, matrix=True):

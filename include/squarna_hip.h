@@ -579,6 +579,28 @@ SQ_API int sq_covariation_stat_pairs(const uint8_t *d_rows, int32_t R, int32_t L
                                      const int32_t *d_pairs, int64_t P, void *d_scratch, size_t scratch_bytes, double *d_mean,
                                      int32_t *d_joint, double *d_raw, double *d_value, uint64_t *d_out, void *hip_stream);
 
+/* ---- covariation statistics with a weight per row (CovariationStatistics(weights=)) ------------------------------
+ * The two entries above with d_weights double[R], one weight per row: finite, 0 <= w <= 2048; R <= 2^22.  A weight is
+ * quantised once, q = rint(w * 2^20) (ties to even), and the joint table is Q[a * 4 + b] (int64) = the sum of q over the rows
+ * with residue a at v and b at w: integer sums, exact and the same in two calls; the weighted count is Q / 2^20.  The
+ * statistics, the means and the corrections are those above on x = Q / 2^20 as doubles (csrc/sq_covar_wstat.h: with integer
+ * weights the bits of the unweighted entries on the repeated rows).  A record is Q[16] (d_joint int64[cap * 16]), S and C.
+ * d_scratch: sq_covariation_wstat_scratch(R, L) bytes, 8-byte aligned (the scratch above and q).
+ * sq_covariation_wstat_scan: every cell with w - v >= minspan, N = (the sum of Q) / 2^20 >= min_rows and C >= min_stat leaves
+ * one record; d_out as above, but d_out[1] = 3 when a weight was not such a number (it then counted as 0).
+ * sq_covariation_wstat_pairs: the records of the P given pairs; d_out[1] = 0, 2 (a pair was not 0 <= v < w < L) or 3.
+ * Asynchronous on hip_stream, allocate nothing; 0, or -1 as above, also for a null d_weights, R > 2^22 and a negative or NaN
+ * min_rows: nothing enqueued. */
+SQ_API size_t sq_covariation_wstat_scratch(int32_t R, int32_t L);
+SQ_API int sq_covariation_wstat_scan(const uint8_t *d_rows, int32_t R, int32_t L, const double *d_weights, int32_t statistic,
+                                     int32_t correction, int32_t minspan, double min_rows, double min_stat, void *d_scratch,
+                                     size_t scratch_bytes, double *d_mean, int64_t *d_flat, int64_t *d_joint, double *d_raw,
+                                     double *d_value, int64_t cap, uint64_t *d_out, void *hip_stream);
+SQ_API int sq_covariation_wstat_pairs(const uint8_t *d_rows, int32_t R, int32_t L, const double *d_weights, int32_t statistic,
+                                      int32_t correction, const int32_t *d_pairs, int64_t P, void *d_scratch, size_t scratch_bytes,
+                                      double *d_mean, int64_t *d_joint, double *d_raw, double *d_value, uint64_t *d_out,
+                                      void *hip_stream);
+
 /* ---- the shuffled-column null of cov (CovariationSignificance) ---------------------------------------------------------
  * Sample k of K permutes the rows of every column of the alignment on its own: row r of column c gets the key
  * z = seed + 0x9E3779B97F4A7C15 * (1 + ((k * L + c) * R + r)) mod 2^64, the splitmix64 finaliser, (z & ~0xFFFF) | r, and row j

@@ -27,7 +27,8 @@ SYMBOLS = ["sq_version", "sq_last_error", "sq_last_capacity", "sq_batch_workspac
            "sq_align_pair_count_scratch", "sq_align_pair_count", "sq_first_fit_scratch", "sq_first_fit_dev",
            "sq_score_scratch", "sq_score_structs_dev", "sq_entropy_scratch", "sq_entropy_rows", "sq_window_pair_count",
            "sq_variant_diff", "sq_duplex_summary", "sq_covariation_scratch", "sq_covariation_scan", "sq_covariation_pairs", "sq_covariation_stat_scratch",
-           "sq_covariation_stat_scan", "sq_covariation_stat_pairs", "sq_covariation_null_scratch", "sq_covariation_null",
+           "sq_covariation_stat_scan", "sq_covariation_stat_pairs", "sq_covariation_wstat_scratch", "sq_covariation_wstat_scan",
+           "sq_covariation_wstat_pairs", "sq_covariation_null_scratch", "sq_covariation_null",
            "sq_covariation_null_planes", "sq_covariation_stat_null_scratch", "sq_covariation_stat_null", "sq_elements_scratch", "sq_elements_rows", "sq_row_identity_scratch", "sq_row_identity", "sq_row_identity_phases"]
 
 BATCH_NO_FP32 = 1
@@ -224,6 +225,13 @@ def load():
                                            C.c_void_p]
     L.sq_covariation_stat_pairs.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                             C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sq_covariation_wstat_scratch.restype = C.c_size_t
+    L.sq_covariation_wstat_scratch.argtypes = [C.c_int32, C.c_int32]
+    L.sq_covariation_wstat_scan.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                            C.c_void_p, C.c_void_p]
+    L.sq_covariation_wstat_pairs.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sq_covariation_null_scratch.restype = C.c_size_t
     L.sq_covariation_null_scratch.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.sq_covariation_null.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,

@@ -19,6 +19,12 @@ pass forms S of every cell for the column means, a second forms it again with C 
 (``sq_covariation_stat_scan``), or the given pairs are looked up (``sq_covariation_stat_pairs``).  No L x L matrix is stored
 and the sums have a fixed order: two calls give the same bits.  An engine without the device methods (the tests' CPU engine,
 the sharded one) gets the same object built with numpy from one-hot matrix products.  ``CovariationStatistics`` prints nothing.
+
+``weights=`` gives every row a weight (``RowIdentity(...).weights()``: near-duplicate rows share one vote).  A weight is
+quantised once to a multiple of 2^-20, q = round(w * 2^20); the joint table is then the sum of q over a cell's rows, an
+integer, and n, na, nb and N above are those sums divided by 2^20, exact doubles (``csrc/sq_covar_wstat.h``;
+``sq_covariation_wstat_scan`` / ``sq_covariation_wstat_pairs`` on the device).  The sums do not depend on the order of the
+rows, two calls give the same bits, and integer weights give the bits of the unweighted call on the repeated rows.
 """
 import math
 
@@ -29,6 +35,11 @@ from .covariation import TYPES, _classes, _device_engine, _open
 from .results import TensorResult
 
 _DEVICE_METHODS = ("covariation_stat_scan", "covariation_stat_pairs")
+_DEVICE_METHODS_W = ("covariation_wstat_scan", "covariation_wstat_pairs")
+#: the fixed point of the row weights, the largest weight and the most weighted rows (csrc/sq_covar_wstat.h)
+WEIGHT_ONE = 1 << 20
+MAX_WEIGHT = 2048.0
+MAX_WEIGHTED_ROWS = 1 << 22
 STATISTICS = ("mi", "gt", "chi")
 CORRECTIONS = (None, "apc", "asc")
 #: the residues of the joint table's two axes: ``joint[:, a * 4 + b]`` counts LETTERS[a] at v with LETTERS[b] at w
@@ -108,6 +119,94 @@ def _host_statistics(rows, given, statistic, correction, minspan, min_rows, min_
     return (cols.reshape(-1, 2), n[at].astype(np.int32).reshape(-1, 16), S[at].reshape(-1), C[at].reshape(-1)) + means
 
 
+def _two_product(a, b):
+    """(p, e) float64 with p = fl(a * b) and p + e = a * b exactly (Dekker's product; numpy has no fma), |a|, |b| < 2^53."""
+    def split(x):
+        t = x * 134217729.0                                          # 2^27 + 1
+        hi = t - (t - x)
+        return hi, x - hi
+    p = a * b
+    (ah, al), (bh, bl) = split(a), split(b)
+    return p, ((ah * bh - p) + ah * bl + al * bh) + al * bl
+
+
+def _host_ratio(a, b, c, d):
+    """a * b / (c * d) of integers below 2^53 held as float64, rounded once (SqCovarWstat::ratio, csrc/sq_covar_wstat.h): the two
+    products exact as a double and its residual each, the quotient of the leading parts corrected by the division's own
+    residual -- or left as it is where both products are exact doubles: the quotient _host_raw forms."""
+    num, num_lo = _two_product(a, b)
+    den, den_lo = _two_product(c, d)
+    q = num / den
+    head, tail = _two_product(q, den)
+    rest = ((num - head) - tail) + (num_lo - q * den_lo)
+    return np.where((num_lo == 0) & (den_lo == 0), q, q + rest / den)
+
+
+def _host_raw_w(Q, statistic):
+    """S float64[...] of the weighted joint tables Q int64[..., 16] (sums of quantised weights): the margins and N are summed as
+    int64, everything becomes a double once, x = Q / 2^20, and the formulas of _host_raw follow on the doubles, the terms added
+    in the table's order; the quotient under the logarithm is _host_ratio's."""
+    one = float(WEIGHT_ONE)
+    sq = Q.reshape(Q.shape[:-1] + (4, 4))
+    N, x = Q.sum(-1) / one, Q / one
+    Qa, Qb = sq.sum(-1).astype(np.float64), sq.sum(-2).astype(np.float64)
+    margins = ((Qa / one)[..., :, None] * (Qb / one)[..., None, :]).reshape(Q.shape)
+    S = np.zeros(Q.shape[:-1], np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for k in range(16):
+            xk, mk = x[..., k], margins[..., k]
+            if statistic == "chi":
+                e = mk / N
+                S = S + np.where(mk > 0, (xk - e) * (xk - e) / e, 0.0)
+            else:
+                weight = xk / N if statistic == "mi" else xk
+                ratio = _host_ratio(Q[..., k].astype(np.float64), Q.sum(-1).astype(np.float64), Qa[..., k >> 2], Qb[..., k & 3])
+                S = S + np.where(xk > 0, weight * np.log(ratio), 0.0)
+    S = np.where(N > 0, S, 0.0)
+    return 2.0 * S if statistic == "gt" else S
+
+
+def _host_statistics_w(rows, q, given, statistic, correction, minspan, min_rows, min_stat):
+    """_host_statistics with the quantised row weights q int64[R]: the joint table is Q int64[P, 16], per cell one int64 matrix
+    product of the first letter's one-hot matrix and the second's times q, and min_rows is compared with the sum of Q / 2^20."""
+    L = rows.shape[1]
+    cls = _classes(rows)
+    hot = [(cls == k).astype(np.int64) for k in range(4)]
+    Q = np.stack([hot[a].T @ (hot[b] * q[:, None]) for a in range(4) for b in range(4)], -1)
+    S = _host_raw_w(Q, statistic)
+    mean, mean_all = _host_means(S) if correction is not None else (np.zeros(L), 0.0)
+    C = _host_corrected(S, mean[:, None], mean[None, :], mean_all, correction)
+    if given is None:
+        v, w = np.indices((L, L))
+        keep = (w > v) & (w - v >= minspan) & (Q.sum(-1) / float(WEIGHT_ONE) >= min_rows)
+        if min_stat is not None:
+            keep &= C >= min_stat
+        at = np.nonzero(keep)                                        # (row-major: sorted by (v, w))
+        cols = np.stack(at, 1).astype(np.int32)
+    else:
+        at, cols = (given[:, 0], given[:, 1]), given.astype(np.int32)
+    means = (mean, np.float64(mean_all)) if correction is not None else (None, None)
+    return (cols.reshape(-1, 2), Q[at].reshape(-1, 16), S[at].reshape(-1), C[at].reshape(-1)) + means
+
+
+def _row_weights(who, weights, R):
+    """weights= as a float64 torch tensor [R] on the device it came on (a sequence or a numpy array: the host); ValueError
+    when it is not R finite numbers in 0 .. MAX_WEIGHT."""
+    import torch
+    try:
+        w = weights.detach() if hasattr(weights, "detach") else torch.from_numpy(np.array(weights, dtype=np.float64))
+        w = w.to(torch.float64).reshape(-1).contiguous()
+    except Exception:
+        raise ValueError("{}: weights is a sequence, an array or a tensor of numbers, one per row".format(who))
+    if int(w.numel()) != R:
+        raise ValueError("{}: weights has {} entries for {} rows".format(who, int(w.numel()), R))
+    if R > MAX_WEIGHTED_ROWS:
+        raise ValueError("{}: weights takes at most 2^22 rows: {}".format(who, R))
+    if not bool((torch.isfinite(w) & (w >= 0) & (w <= MAX_WEIGHT)).all()):         # (one flag comes to the host, not the weights)
+        raise ValueError("{}: weights are finite numbers from 0 to {:g}".format(who, MAX_WEIGHT))
+    return w
+
+
 class CovariationStatisticsResult(TensorResult):
     """What ``CovariationStatistics`` computes for an alignment of R rows and L columns.
 
@@ -117,26 +216,33 @@ class CovariationStatisticsResult(TensorResult):
     otherwise --, ``joint`` int32[P, 16] -- the joint table, cell ``a * 4 + b`` (``CELLS``) = the rows with ``LETTERS[a]`` at v
     and ``LETTERS[b]`` at w --, ``raw`` float64[P] = S, ``value`` float64[P] = C, and with a correction ``col_mean`` float64[L]
     and ``mean_all`` (a 0-dim float64 tensor); both are None without one.  Derived with torch ops: ``rows`` (N),
-    ``marginals()``, ``canonical()``, ``to_matrix()``, ``top()``."""
+    ``marginals()``, ``canonical()``, ``to_matrix()``, ``top()``.
+
+    With ``weights=``: ``weights`` float64[R], the weights as given, on ``device`` (None without), and ``joint`` is
+    float64[P, 16], the sum of the rows' quantised weights per cell (multiples of 2^-20, exact); ``rows``, ``marginals()``,
+    ``canonical()``, ``of()`` and ``to_matrix()`` of a cell or of "rows" are then float64 as well."""
 
     LETTERS, CELLS, TYPES = LETTERS, CELLS, TYPES
-    _TENSORS = ("value", "pair_cols", "joint", "raw", "col_mean", "mean_all")
+    _TENSORS = ("value", "pair_cols", "joint", "raw", "col_mean", "mean_all", "weights")
 
-    def __init__(self, names, sequences, statistic, correction, mode, source, pair_cols, joint, raw, value, col_mean, mean_all):
+    def __init__(self, names, sequences, statistic, correction, mode, source, pair_cols, joint, raw, value, col_mean, mean_all,
+                 weights=None):
         self.names, self.sequences, self.R, self.L = names, sequences, len(sequences), len(sequences[0])
         self.statistic, self.correction, self.mode, self.source = statistic, correction, mode, source
         self.pair_cols, self.joint, self.raw, self.value, self.col_mean, self.mean_all = pair_cols, joint, raw, value, col_mean, mean_all
+        self.weights = weights
 
     def __len__(self):
         return int(self.value.numel())
 
     @property
     def rows(self):
-        """int32[P]: N, the rows that hold a residue in both columns."""
+        """int32[P]: N, the rows that hold a residue in both columns (float64[P] with weights: their weights' sum)."""
         return self.joint.sum(1, dtype=self.joint.dtype)
 
     def marginals(self):
-        """(na int32[P, 4], nb int32[P, 4]): the rows with each residue of ``LETTERS`` at v and at w, among the N rows."""
+        """(na int32[P, 4], nb int32[P, 4]): the rows with each residue of ``LETTERS`` at v and at w, among the N rows (float64 with
+        weights)."""
         sq = self.joint.reshape(-1, 4, 4)
         return sq.sum(2, dtype=self.joint.dtype), sq.sum(1, dtype=self.joint.dtype)
 
@@ -189,7 +295,7 @@ class CovariationStatisticsResult(TensorResult):
 
 
 def CovariationStatistics(inputfile=None, fileformat="unknown", inputformat="qtrf", sequences=None, names=None, alignment=None, pairs=None,
-                          statistic="gt", correction="apc", minspan=4, min_rows=1, min_stat=None, ignorewarn=False):
+                          statistic="gt", correction="apc", minspan=4, min_rows=1, min_stat=None, ignorewarn=False, weights=None):
     """Covariation statistics of pairs of columns of an alignment, returned as a :class:`CovariationStatisticsResult`.
 
     The inputs and ``pairs`` mean what they mean in ``Covariation``.  ``statistic``: "mi", "gt" or "chi"; ``correction``:
@@ -200,7 +306,13 @@ def CovariationStatistics(inputfile=None, fileformat="unknown", inputformat="qtr
 
     A record is 88 bytes on the device.  With ``min_stat=None`` a scan returns nearly every cell in scope, about 44 L^2 bytes
     (1.1 GB at 5,000 columns): up to 2^20 cells in scope the result buffers are sized for all of them at once, beyond that a
-    first scan counts and a second stores (``_SCAN_CAP``).  Set ``min_stat`` to get the pairs that matter."""
+    first scan counts and a second stores (``_SCAN_CAP``).  Set ``min_stat`` to get the pairs that matter.
+
+    ``weights``: None, or one weight per row as a sequence, a numpy array or a torch tensor on any device, taken as float64
+    (``RowIdentity(...).weights()`` goes in as it is and stays on its device).  A weight is a finite number from 0 to 2048;
+    a row of weight 0 takes part in nothing.  The joint table, N and the statistics are then those of the weighted rows (the
+    module's text), ``min_rows`` may be a float and is compared with the weighted N, and the result has ``weights`` and a
+    float64 ``joint``.  ValueError for a wrong length, a NaN, an infinite or negative weight or one above 2048."""
     import torch
     who = "CovariationStatistics"
     if statistic not in STATISTICS:
@@ -211,10 +323,17 @@ def CovariationStatistics(inputfile=None, fileformat="unknown", inputformat="qtr
         if isinstance(min_stat, bool) or not isinstance(min_stat, (int, float, np.integer, np.floating)) or math.isnan(min_stat):
             raise ValueError("{}: min_stat is a number or None: {!r}".format(who, min_stat))
         min_stat = float(min_stat)
+    if weights is not None:                                          # (a float is allowed: _open takes the other thresholds)
+        if isinstance(min_rows, bool) or not isinstance(min_rows, (int, float, np.integer, np.floating)) or not min_rows >= 0:
+            raise ValueError("{}: with weights min_rows is a non-negative number: {!r}".format(who, min_rows))
+        weighted_rows, min_rows = float(min_rows), 0
     names, seqs, (minspan, min_rows, _), given, rows = _open(who, inputfile, fileformat, inputformat, sequences, names, alignment, pairs,
                                                             minspan, min_rows, 0, ignorewarn)
     L = rows.shape[1]
     eng = _engine.get_engine()
+    if weights is not None:
+        return _weighted(who, eng, names, seqs, rows, given, alignment, _row_weights(who, weights, rows.shape[0]), statistic, correction,
+                         minspan, weighted_rows, min_stat)
     on_device = _device_engine(eng, _DEVICE_METHODS)
     if on_device:
         if alignment is not None and alignment.device.type == "cuda":
@@ -244,3 +363,44 @@ def CovariationStatistics(inputfile=None, fileformat="unknown", inputformat="qtr
             for a in _host_statistics(rows, given, statistic, correction, minspan, min_rows, min_stat))
     return CovariationStatisticsResult(names, seqs, statistic, correction, "scan" if given is None else "pairs",
                                        "device" if on_device else "host", cols, joint, raw, value, col_mean, mean_all)
+
+
+def _weighted(who, eng, names, seqs, rows, given, alignment, weights, statistic, correction, minspan, min_rows, min_stat):
+    """CovariationStatistics with weights= (a float64 tensor [R] from _row_weights): the device entries of the weighted
+    statistics when the engine has both, numpy otherwise."""
+    import torch
+    L = rows.shape[1]
+    on_device = _device_engine(eng, _DEVICE_METHODS_W)
+    if on_device:
+        if weights.is_cuda:
+            dev = weights.device
+        elif alignment is not None and alignment.device.type == "cuda":
+            dev = alignment.device
+        elif hasattr(given, "is_cuda") and given.is_cuda:
+            dev = given.device
+        else:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        d_rows, weights = torch.from_numpy(rows.copy()).to(dev), weights.to(dev)
+        if given is None:
+            span = L - max(minspan, 1)                               # the cells in scope: span * (span + 1) / 2
+            cap = max(span * (span + 1) // 2, 1) if min_stat is None and span * (span + 1) // 2 <= _SCAN_CAP else None
+            flat, Q, raw, value, mean = eng.covariation_wstat_scan(d_rows, weights, statistic, correction, minspan, min_rows, min_stat, cap=cap)
+            flat, order = torch.sort(flat)
+            cols, Q, raw, value = torch.stack((flat // L, flat % L), 1).to(torch.int32), Q[order], raw[order], value[order]
+        else:
+            cols = (given if hasattr(given, "dim") else torch.from_numpy(given)).to(device=dev, dtype=torch.int32).contiguous()
+            Q, raw, value, mean = eng.covariation_wstat_pairs(d_rows, weights, cols, statistic, correction)
+        col_mean, mean_all = (mean[:L], mean[L]) if mean is not None else (None, None)
+    else:
+        if given is not None:
+            given = (given.cpu() if hasattr(given, "dim") else torch.from_numpy(given)).to(torch.int64).numpy().reshape(-1, 2)
+            if len(given) and not ((given[:, 0] >= 0) & (given[:, 0] < given[:, 1]) & (given[:, 1] < L)).all():
+                raise RuntimeError("%s: a pair is not 0 <= v < w < %d columns" % (who, L))
+        weights = weights.cpu()
+        q = np.rint(weights.numpy() * float(WEIGHT_ONE)).astype(np.int64)    # (the product is exact; ties to even)
+        cols, Q, raw, value, col_mean, mean_all = (
+            None if a is None else torch.from_numpy(np.array(a))     # (np.array: mean_all stays 0-dim)
+            for a in _host_statistics_w(rows, q, given, statistic, correction, minspan, min_rows, min_stat))
+    joint = Q.double() * (1.0 / WEIGHT_ONE)                          # (a power of two: exact)
+    return CovariationStatisticsResult(names, seqs, statistic, correction, "scan" if given is None else "pairs",
+                                       "device" if on_device else "host", cols, joint, raw, value, col_mean, mean_all, weights)

@@ -79,7 +79,8 @@ def CovariationStatisticsSignificance(inputfile=None, fileformat="unknown", inpu
     column permuted on its own by a fixed function of ``seed`` (an int in [0, 2^64)); its cells are the v < w with
     ``w - v >= minspan``, whatever ``min_rows`` and ``min_stat``, and a cell's value is C with the column means of its own
     shuffled sample.  Gaps and other bytes move like letters.  At most 65,535 rows; on the device at most
-    ``device_calls.COVAR_NULL_MAX_ROWS``."""
+    ``device_calls.COVAR_NULL_MAX_ROWS``.  Row weights (``CovariationStatistics(weights=)``) are not taken here: ``.observed``
+    and the null count every row once."""
     import torch
     who = "CovariationStatisticsSignificance"
     if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or samples < 1:

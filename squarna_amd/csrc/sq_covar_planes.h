@@ -9,3 +9,8 @@
 
 int covar_planes(const char *who, const uint8_t *d_rows, int32_t R, int32_t L, void *d_scratch, size_t scratch_bytes, uint64_t *d_out,
                  hipStream_t st);
+
+// The end of a pass 1 over the statistics of every pair of columns (sq_covar_stat_dev.hip defines it; sq_covar_stat.h has the
+// order of the sums): sq_covar_stat_reduce_kernel and sq_covar_stat_total_kernel enqueued on st, d_mean[0 .. L] from the
+// partial column sums.
+int covar_stat_means(const double *partial, int32_t L, double *d_mean, hipStream_t st);

@@ -251,6 +251,16 @@ extern "C" size_t sq_covariation_stat_scratch(int32_t R, int32_t L)
     return R < 1 || L < 1 ? 0 : (size_t)SqCovarStat::scratch_words(R, L) * 8;
 }
 
+// The two reductions behind a pass 1: d_mean[0 .. L] from its partial column sums (sq_covar_planes.h: the weighted entries of
+// sq_covar_wstat_dev.hip end their pass 1 with the same two kernels).
+int covar_stat_means(const double *partial, int32_t L, double *d_mean, hipStream_t st)
+{
+    hipLaunchKernelGGL(sq_covar_stat_reduce_kernel, dim3((unsigned)(((int64_t)L + 255) / 256)), dim3(256), 0, st, partial, L, d_mean);
+    if (int rc = sq_check(hipGetLastError(), "sq_covar_stat_reduce_kernel")) return rc;
+    hipLaunchKernelGGL(sq_covar_stat_total_kernel, dim3(1), dim3(256), 0, st, L, d_mean);
+    return sq_check(hipGetLastError(), "sq_covar_stat_total_kernel");
+}
+
 // The checks both entries share; then the planes in d_scratch and, with a correction, pass 1 and the two reductions: d_mean.
 static int stat_open(const char *who, const uint8_t *d_rows, int32_t R, int32_t L, int32_t stat, int32_t corr, void *d_scratch,
                      size_t scratch_bytes, double *d_mean, uint64_t *d_out, hipStream_t st)
@@ -270,11 +280,7 @@ static int stat_open(const char *who, const uint8_t *d_rows, int32_t R, int32_t 
     const unsigned blocks = (unsigned)std::min<int64_t>(SqCovar::tile_count(SqCovarStat::tiles(L)), SQ_COVSTAT_MAX_BLOCKS);
     hipLaunchKernelGGL(sq_covar_stat_sums_kernel, dim3(blocks), dim3(256), 0, st, plane, R, L, stat, partial);
     if (int rc = sq_check(hipGetLastError(), "sq_covar_stat_sums_kernel")) return rc;
-    hipLaunchKernelGGL(sq_covar_stat_reduce_kernel, dim3((unsigned)(((int64_t)L + 255) / 256)), dim3(256), 0, st, (const double *)partial, L,
-                       d_mean);
-    if (int rc = sq_check(hipGetLastError(), "sq_covar_stat_reduce_kernel")) return rc;
-    hipLaunchKernelGGL(sq_covar_stat_total_kernel, dim3(1), dim3(256), 0, st, L, d_mean);
-    return sq_check(hipGetLastError(), "sq_covar_stat_total_kernel");
+    return covar_stat_means(partial, L, d_mean, st);
 }
 
 extern "C" int sq_covariation_stat_scan(const uint8_t *d_rows, int32_t R, int32_t L, int32_t statistic, int32_t correction, int32_t minspan,
@@ -482,11 +488,7 @@ extern "C" int sq_covariation_stat_null(const uint8_t *d_rows, int32_t R, int32_
             double *partial = d_partial + s * per_partial, *mean = d_mean + s * per_mean;
             hipLaunchKernelGGL(sq_covar_stat_sums_kernel, dim3(pass1), dim3(256), 0, st, plane, R, L, statistic, partial);
             if (int rc = sq_check(hipGetLastError(), "sq_covar_stat_sums_kernel")) return rc;
-            hipLaunchKernelGGL(sq_covar_stat_reduce_kernel, dim3((unsigned)(((int64_t)L + 255) / 256)), dim3(256), 0, st, (const double *)partial,
-                               L, mean);
-            if (int rc = sq_check(hipGetLastError(), "sq_covar_stat_reduce_kernel")) return rc;
-            hipLaunchKernelGGL(sq_covar_stat_total_kernel, dim3(1), dim3(256), 0, st, L, mean);
-            if (int rc = sq_check(hipGetLastError(), "sq_covar_stat_total_kernel")) return rc;
+            if (int rc = covar_stat_means(partial, L, mean, st)) return rc;
         }
         // The scan's grid: the batch's samples times as many blocks as keep the whole grid near SQ_COVSTAT_MAX_BLOCKS; a block
         // walks the rest of its sample's tiles by grid stride.

@@ -26,6 +26,11 @@ COVAR_STAT_MAX_BLOCKS = 2048
 #: the statistics and the corrections of sq_covariation_stat_scan / _pairs by name (SQ_COVSTAT_*, csrc/sq_covar_stat.h)
 COVAR_STATISTICS = ("mi", "gt", "chi")
 COVAR_CORRECTIONS = (None, "apc", "asc")
+#: the fixed point of the row weights of sq_covariation_wstat_scan / _pairs, the largest weight and the most rows they take
+#: (SQ_COVWSTAT_ONE, SQ_COVWSTAT_MAX_WEIGHT, SQ_COVWSTAT_MAX_ROWS, csrc/sq_covar_wstat.h)
+COVAR_WSTAT_ONE = 1 << 20
+COVAR_WSTAT_MAX_WEIGHT = 2048.0
+COVAR_WSTAT_MAX_ROWS = 1 << 22
 #: the most rows sq_covariation_null shuffles on the device and the bins its scan keeps in LDS (SQ_COVNULL_MAX_ROWS,
 #: SQ_COVNULL_LDS_BINS, csrc/sq_covar_null.h)
 COVAR_NULL_MAX_ROWS = 4096
@@ -360,6 +365,65 @@ class DeviceCalls:
                                                    _ptr(mean), _ptr(joint if P else None), _ptr(raw if P else None),
                                                    _ptr(value if P else None), _ptr(out), _stream(dev)))
             _result_words(out, "sq_covariation_stat_pairs: a pair is not 0 <= v < w < %d columns" % Lcols)
+        return joint, raw, value, mean
+
+    def _covariation_wstat_buffers(self, rows, weights, statistic, correction):
+        """What covariation_wstat_scan and covariation_wstat_pairs share: (stat, corr, scratch, its bytes, mean or None)."""
+        import torch
+        L = _lib.load()
+        assert rows.dtype == torch.uint8 and rows.is_cuda and rows.dim() == 2 and rows.is_contiguous()
+        R, Lcols = int(rows.shape[0]), int(rows.shape[1])
+        assert weights.dtype == torch.float64 and weights.device == rows.device and tuple(weights.shape) == (R,) and weights.is_contiguous()
+        stat, corr = COVAR_STATISTICS.index(statistic), COVAR_CORRECTIONS.index(correction)
+        nbytes = int(L.sq_covariation_wstat_scratch(R, Lcols))
+        scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=rows.device)
+        mean = torch.empty(Lcols + 1, dtype=torch.float64, device=rows.device) if corr else None
+        return stat, corr, scratch, nbytes, mean
+
+    def covariation_wstat_scan(self, rows, weights, statistic="gt", correction="apc", minspan=4, min_rows=1.0, min_stat=None, cap=None):
+        """covariation_stat_scan with a weight per row (sq_covariation_wstat_scan): weights = float64 device tensor [R], each
+        finite and in 0 .. 2048 (RuntimeError otherwise), quantised to multiples of 1 / COVAR_WSTAT_ONE.  Returns the device
+        tensors (flat int64, joint int64[P, 16] = Q, the sums of the quantised weights of the rows of each cell: the weighted
+        counts times COVAR_WSTAT_ONE, raw, value, mean) as covariation_stat_scan does; min_rows is a float and compared with the
+        weighted rows of a cell, the sum of Q / COVAR_WSTAT_ONE."""
+        import torch
+        L = _lib.load()
+        dev, R, Lcols = rows.device, int(rows.shape[0]), int(rows.shape[1])
+        cap = 1 << 16 if cap is None else int(cap)
+        floor = float("-inf") if min_stat is None else float(min_stat)
+
+        def call(res, cap, out):
+            _lib.check(L.sq_covariation_wstat_scan(_ptr(rows), R, Lcols, _ptr(weights), stat, corr, int(minspan), float(min_rows), floor,
+                                                   _ptr(scratch), nbytes, _ptr(mean), _ptr(res[0]), _ptr(res[1]), _ptr(res[2]), _ptr(res[3]), cap,
+                                                   _ptr(out), _stream(dev)))
+
+        with torch.cuda.device(dev):
+            stat, corr, scratch, nbytes, mean = self._covariation_wstat_buffers(rows, weights, statistic, correction)
+            return _call_until_fits(dev, cap, (torch.int64, (torch.int64, 16), torch.float64, torch.float64), call,
+                                    "sq_covariation_wstat_scan: a weight is not a finite number in 0 .. 2048") + (mean,)
+
+    def covariation_wstat_pairs(self, rows, weights, pairs, statistic="gt", correction="apc"):
+        """covariation_stat_pairs with a weight per row (sq_covariation_wstat_pairs; the weights and Q as covariation_wstat_scan
+        has them).  Returns the device tensors (joint int64[P, 16] = Q, raw float64[P], value float64[P], mean float64[L + 1] or
+        None) in the pairs' order; RuntimeError for a bad weight or a bad pair.  Only the two result words come to the host."""
+        import torch
+        L = _lib.load()
+        assert pairs.dtype == torch.int32 and pairs.dim() == 2 and int(pairs.shape[1]) == 2 and pairs.device == rows.device
+        dev, R, Lcols, P = rows.device, int(rows.shape[0]), int(rows.shape[1]), int(pairs.shape[0])
+        pairs = pairs.contiguous()
+        with torch.cuda.device(dev):
+            stat, corr, scratch, nbytes, mean = self._covariation_wstat_buffers(rows, weights, statistic, correction)
+            joint = torch.empty((P, 16), dtype=torch.int64, device=dev)
+            raw, value = torch.empty(P, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.float64, device=dev)
+            out = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.check(L.sq_covariation_wstat_pairs(_ptr(rows), R, Lcols, _ptr(weights), stat, corr, _ptr(pairs if P else None), P,
+                                                    _ptr(scratch), nbytes, _ptr(mean), _ptr(joint if P else None), _ptr(raw if P else None),
+                                                    _ptr(value if P else None), _ptr(out), _stream(dev)))
+            status = out.tolist()[1]
+            if status == 3:
+                raise RuntimeError("sq_covariation_wstat_pairs: a weight is not a finite number in 0 .. 2048")
+            if status:
+                raise RuntimeError("sq_covariation_wstat_pairs: a pair is not 0 <= v < w < %d columns" % Lcols)
         return joint, raw, value, mean
 
     def covariation_null_planes(self, rows, k, seed, count=None):

@@ -649,6 +649,20 @@ SQ_API int sq_covariation_stat_null(const uint8_t *d_rows, int32_t R, int32_t L,
                                     int32_t K, uint64_t seed, int32_t batch, void *d_scratch, size_t scratch_bytes, int64_t *d_hist,
                                     int32_t *d_own_ge, double *d_null_max, uint64_t *d_out, void *hip_stream);
 
+/* ---- the shuffled-column null of the weighted covariation statistics (CovariationStatisticsSignificance(weights=)) ------
+ * sq_covariation_stat_null with the joint tables of sq_covariation_wstat_scan: d_weights double[R], each finite and in
+ * 0 .. 2048, quantised once as there.  The weights belong to the row slots: sample k permutes the rows of every column as
+ * sq_covariation_null does and row r keeps its weight, so a null cell's value is the C that sq_covariation_wstat_scan gives
+ * for the shuffled rows and the same weights, bit for bit (csrc/sq_covar_wstat_null.h).  A row of weight 0 is shuffled and
+ * counts nothing.  Every other argument, output and error is sq_covariation_stat_null's; d_out[1] = 0, 2 (a pair was not
+ * 0 <= v < w < L; it counts nothing) or 3 (a weight was not a finite number in 0 .. 2048; it counts as 0).  The scratch
+ * (sq_covariation_wstat_null_scratch(R, L, batch) bytes) is that of sq_covariation_stat_null, then the quantised weights. */
+SQ_API size_t sq_covariation_wstat_null_scratch(int32_t R, int32_t L, int32_t batch);
+SQ_API int sq_covariation_wstat_null(const uint8_t *d_rows, int32_t R, int32_t L, int32_t statistic, int32_t correction, int32_t minspan,
+                                     const int32_t *d_pairs, const double *d_value, int64_t P, const double *d_thresholds, int64_t U,
+                                     int32_t K, uint64_t seed, int32_t batch, void *d_scratch, size_t scratch_bytes, int64_t *d_hist,
+                                     int32_t *d_own_ge, double *d_null_max, uint64_t *d_out, void *hip_stream, const double *d_weights);
+
 /* ---- row identities, neighbour counts and the redundancy filter of an alignment (RowIdentity) ----------------------------
  * d_rows uint8[R * L] as for the covariation entries, the bytes classified in the same way; a residue is any non-gap, a base
  * is A, C, G or U, and "other" matches nothing.  For rows a, b: same[a, b] = the columns where both hold the same base,

@@ -166,13 +166,18 @@ def _host_raw_w(Q, statistic):
     return 2.0 * S if statistic == "gt" else S
 
 
-def _host_statistics_w(rows, q, given, statistic, correction, minspan, min_rows, min_stat):
-    """_host_statistics with the quantised row weights q int64[R]: the joint table is Q int64[P, 16], per cell one int64 matrix
-    product of the first letter's one-hot matrix and the second's times q, and min_rows is compared with the sum of Q / 2^20."""
-    L = rows.shape[1]
-    cls = _classes(rows)
+def _host_tables_w(cls, q):
+    """int64[L, L, 16]: _host_tables with the quantised row weights q int64[R]: per cell of the table one int64 matrix product
+    of the first letter's one-hot matrix and the second's times q."""
     hot = [(cls == k).astype(np.int64) for k in range(4)]
-    Q = np.stack([hot[a].T @ (hot[b] * q[:, None]) for a in range(4) for b in range(4)], -1)
+    return np.stack([hot[a].T @ (hot[b] * q[:, None]) for a in range(4) for b in range(4)], -1)
+
+
+def _host_statistics_w(rows, q, given, statistic, correction, minspan, min_rows, min_stat):
+    """_host_statistics with the quantised row weights q int64[R]: the joint table is Q int64[P, 16] (_host_tables_w), and
+    min_rows is compared with the sum of Q / 2^20."""
+    L = rows.shape[1]
+    Q = _host_tables_w(_classes(rows), q)
     S = _host_raw_w(Q, statistic)
     mean, mean_all = _host_means(S) if correction is not None else (np.zeros(L), 0.0)
     C = _host_corrected(S, mean[:, None], mean[None, :], mean_all, correction)

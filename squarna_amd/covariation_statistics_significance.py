@@ -14,22 +14,44 @@ as bit planes on the device, each sample's means are formed by the first pass of
 pass is reduced to a histogram against the observed values; no record and no L x L matrix is stored).  An engine without the
 device method (the tests' CPU engine, the sharded one) gets the same object with numpy; its counts can differ from the
 device's only where a null value lies within the float bound of an observed one.
+
+``weights=`` gives the null of the weighted statistics (``CovariationStatistics(weights=)``).  The weights belong to the row
+slots, not to the letters: sample k permutes the rows of every column exactly as without weights, and row r of the shuffled
+alignment keeps weight r.  A null cell's value is then what ``CovariationStatistics(weights=weights)`` returns for the
+shuffled alignment (``sq_covariation_wstat_null`` on the device: the bits of ``sq_covariation_wstat_scan`` on the shuffled
+rows).  A row of weight 0 takes part in the shuffle -- its letters move -- and counts nothing.  The shuffle keeps each
+column's letter counts; it does not keep each column's weighted composition: that is the plain meaning of "the same analysis
+on a shuffled alignment", and what a hand-written loop over shuffled alignments would do.
 """
 import numpy as np
 
 from . import engine as _engine
 from .covariation import _classes, _device_engine
 from .covariation_significance import _MASK, SignificanceResult, _shuffled_classes, scope_cells
-from .covariation_statistics import (_DEVICE_METHODS, CovariationStatistics, _host_corrected, _host_means, _host_raw, _host_tables)
+from .covariation_statistics import (_DEVICE_METHODS, _DEVICE_METHODS_W, WEIGHT_ONE, CovariationStatistics, _host_corrected, _host_means,
+                                     _host_raw, _host_raw_w, _host_tables, _host_tables_w)
 
 _NULL_METHODS = _DEVICE_METHODS + ("covariation_stat_null",)
+_NULL_METHODS_W = _DEVICE_METHODS_W + ("covariation_wstat_null",)
 
 
 def _host_stat_null(rows, pairs, value, statistic, correction, minspan, samples, seed):
     """(null_ge int64[P], own_ge int32[P], null_max float64[samples]) with numpy: per sample an argsort of the sort keys and
     the one-hot matrix products, means and corrections of CovariationStatistics' numpy path (deliberately not the kernels'
     form)."""
-    cls = _classes(rows)
+    return _host_null(_classes(rows), lambda cls: _host_raw(_host_tables(cls), statistic), pairs, value, correction, minspan, samples, seed)
+
+
+def _host_stat_null_w(rows, q, pairs, value, statistic, correction, minspan, samples, seed):
+    """_host_stat_null with the quantised row weights q int64[R]: row r of every shuffled sample keeps q[r], and S is that of
+    CovariationStatistics(weights=)'s numpy path on the weighted tables."""
+    return _host_null(_classes(rows), lambda cls: _host_raw_w(_host_tables_w(cls, q), statistic), pairs, value, correction, minspan, samples,
+                      seed)
+
+
+def _host_null(cls, raw_of, pairs, value, correction, minspan, samples, seed):
+    """What the two numpy nulls share: cls uint8[R, L] the class bytes of the rows, raw_of(class bytes) = S float64[L, L] of an
+    alignment."""
     L, P = cls.shape[1], len(value)
     thresholds = np.unique(value)
     hist = np.zeros(len(thresholds) + 1, np.int64)
@@ -37,7 +59,7 @@ def _host_stat_null(rows, pairs, value, statistic, correction, minspan, samples,
     v, w = np.indices((L, L))
     scope = (w > v) & (w - v >= minspan)
     for k in range(samples):
-        S = _host_raw(_host_tables(_shuffled_classes(cls, k, seed)), statistic)
+        S = raw_of(_shuffled_classes(cls, k, seed))
         mean, mean_all = _host_means(S) if correction is not None else (np.zeros(L), 0.0)
         null = _host_corrected(S, mean[:, None], mean[None, :], mean_all, correction)
         cells = null[scope]
@@ -59,7 +81,12 @@ class StatisticsSignificanceResult(SignificanceResult):
     over all samples and in-scope cells, the null cells with ``C_null >= value[p]`` (the pooled null) --, ``own_ge`` int32[P]
     -- the samples in which the same cell (v, w) has ``C_null >= value[p]`` (the per-pair permutation test) --, ``null_max``
     float64[K] -- the largest ``C_null`` of a sample's in-scope cells, ``-inf`` without one (the max-statistic, family-wise
-    test).  All comparisons are IEEE ``>=`` on doubles; no value is NaN."""
+    test).  All comparisons are IEEE ``>=`` on doubles; no value is NaN.  ``weights``: that of ``observed`` (float64[R], or None
+    without ``weights=``)."""
+
+    @property
+    def weights(self):
+        return self.observed.weights
 
     def max_ge(self):
         """int64[P]: the samples whose largest null value reaches value[p]."""
@@ -70,7 +97,7 @@ class StatisticsSignificanceResult(SignificanceResult):
 
 def CovariationStatisticsSignificance(inputfile=None, fileformat="unknown", inputformat="qtrf", sequences=None, names=None,
                                       alignment=None, pairs=None, statistic="gt", correction="apc", minspan=4, min_rows=1,
-                                      min_stat=None, samples=100, seed=0, ignorewarn=False):
+                                      min_stat=None, samples=100, seed=0, ignorewarn=False, weights=None):
     """The observed covariation statistic of pairs of columns of an alignment against a shuffled-column null, returned as a
     :class:`StatisticsSignificanceResult`.
 
@@ -79,8 +106,14 @@ def CovariationStatisticsSignificance(inputfile=None, fileformat="unknown", inpu
     column permuted on its own by a fixed function of ``seed`` (an int in [0, 2^64)); its cells are the v < w with
     ``w - v >= minspan``, whatever ``min_rows`` and ``min_stat``, and a cell's value is C with the column means of its own
     shuffled sample.  Gaps and other bytes move like letters.  At most 65,535 rows; on the device at most
-    ``device_calls.COVAR_NULL_MAX_ROWS``.  Row weights (``CovariationStatistics(weights=)``) are not taken here: ``.observed``
-    and the null count every row once."""
+    ``device_calls.COVAR_NULL_MAX_ROWS``.
+
+    ``weights``: None, or one weight per row as ``CovariationStatistics`` takes them (finite, 0 to 2048; ``min_rows`` may then
+    be a float and is compared with the weighted N; weights on a CUDA device decide the device).  ``.observed`` is
+    ``CovariationStatistics(..., weights=weights)`` and the null is that of the weighted statistic: the rows of every column
+    are permuted exactly as without weights and row r keeps weight r, so a null cell's value is what
+    ``CovariationStatistics(weights=weights)`` returns for the shuffled alignment.  A row of weight 0 is shuffled and counts
+    nothing.  The shuffle keeps each column's letter counts, not its weighted composition.  The result has ``weights``."""
     import torch
     who = "CovariationStatisticsSignificance"
     if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or samples < 1:
@@ -89,14 +122,14 @@ def CovariationStatisticsSignificance(inputfile=None, fileformat="unknown", inpu
         raise ValueError("{}: seed is an integer in [0, 2^64): {!r}".format(who, seed))
     samples, seed = int(samples), int(seed)
     eng = _engine.get_engine()
-    on_device = _device_engine(eng, _NULL_METHODS)
+    on_device = _device_engine(eng, _NULL_METHODS if weights is None else _NULL_METHODS_W)
     rows_cap = 65535
     if on_device:
         from .device_calls import COVAR_NULL_MAX_ROWS as rows_cap
     if sequences is not None and len(sequences) > rows_cap:        # (before anything is computed; any other input: below)
         _refuse_rows(who, len(sequences))
     observed = CovariationStatistics(inputfile, fileformat, inputformat, sequences, names, alignment, pairs, statistic, correction, minspan,
-                                     min_rows, min_stat, ignorewarn)
+                                     min_rows, min_stat, ignorewarn, weights)
     R, L, minspan = observed.R, observed.L, int(minspan)
     if R > rows_cap:
         _refuse_rows(who, R)
@@ -104,12 +137,21 @@ def CovariationStatisticsSignificance(inputfile=None, fileformat="unknown", inpu
     rows = np.frombuffer("".join(observed.sequences).encode("latin-1", "replace"), np.uint8).reshape(R, L)
     if on_device:
         d_rows = torch.from_numpy(rows.copy()).to(observed.device)
-        null_ge, own_ge, null_max = eng.covariation_stat_null(d_rows, observed.pair_cols, observed.value, statistic, correction, minspan,
-                                                              samples, seed)
+        if weights is None:
+            null_ge, own_ge, null_max = eng.covariation_stat_null(d_rows, observed.pair_cols, observed.value, statistic, correction, minspan,
+                                                                  samples, seed)
+        else:
+            null_ge, own_ge, null_max = eng.covariation_wstat_null(d_rows, observed.weights, observed.pair_cols, observed.value, statistic,
+                                                                   correction, minspan, samples, seed)
     else:
         host = observed.cpu()
-        null_ge, own_ge, null_max = (torch.from_numpy(np.ascontiguousarray(a)).to(observed.device) for a in _host_stat_null(
-            rows, host.pair_cols.numpy().astype(np.int64), host.value.numpy(), statistic, correction, minspan, samples, seed))
+        given = (rows, host.pair_cols.numpy().astype(np.int64), host.value.numpy(), statistic, correction, minspan, samples, seed)
+        if weights is None:
+            null = _host_stat_null(*given)
+        else:
+            q = np.rint(host.weights.numpy() * float(WEIGHT_ONE)).astype(np.int64)  # (as CovariationStatistics quantised them)
+            null = _host_stat_null_w(rows, q, *given[1:])
+        null_ge, own_ge, null_max = (torch.from_numpy(np.ascontiguousarray(a)).to(observed.device) for a in null)
     return StatisticsSignificanceResult(observed, samples, seed, samples * scope_cells(L, minspan), "device" if on_device else "host",
                                         null_ge, own_ge, null_max)
 

@@ -437,6 +437,13 @@ extern "C" __global__ __launch_bounds__(256) void sq_covar_stat_null_max_kernel(
     if (k < K) null_max[k] = SqCovarStatNull::bits(SqCovarStatNull::unkey(null_max[k]));
 }
 
+// (sq_covar_planes.h: the weighted null of sq_covar_wstat_null_dev.hip ends with the same kernel)
+int covar_stat_null_max(unsigned long long *d_key, int32_t K, hipStream_t st)
+{
+    hipLaunchKernelGGL(sq_covar_stat_null_max_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, d_key, K);
+    return sq_check(hipGetLastError(), "sq_covar_stat_null_max_kernel");
+}
+
 extern "C" size_t sq_covariation_stat_null_scratch(int32_t R, int32_t L, int32_t batch)
 {
     return R < 1 || L < 1 || batch < 1 ? 0 : (size_t)SqCovarStatNull::scratch_words(R, L, batch) * 8;
@@ -504,6 +511,5 @@ extern "C" int sq_covariation_stat_null(const uint8_t *d_rows, int32_t R, int32_
                            (unsigned long long *)d_out);
         if (int rc = sq_check(hipGetLastError(), "sq_covar_stat_null_pairs_kernel")) return rc;
     }
-    hipLaunchKernelGGL(sq_covar_stat_null_max_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, d_key, K);
-    return sq_check(hipGetLastError(), "sq_covar_stat_null_max_kernel");
+    return covar_stat_null_max(d_key, K, st);
 }

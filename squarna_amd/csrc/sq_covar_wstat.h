@@ -32,10 +32,11 @@
 // The column means, mean_all, SqCovarStat::corrected(), SqCovar::in_scope(), the tile walk and the order of every float sum
 // are those of sq_covar_stat.h / sq_covar_stat_dev.hip.
 //
-// LDS.  sq_covar_wstat_lds() places the regions of a block of each of the three kernels; the launch site takes `total` from
-// it and the kernel carves with it (as sq_launch_lds.h does for the launched kernels).  Every offset is a multiple of 16 and
-// the total stays below 64 KB: no limit is raised.  tests/native/covar_wstat_host.cpp checks the layout and runs the header
-// as one thread.
+// LDS.  sq_covar_wstat_lds() places the regions of a block of each of the three kernels, and of the scan kernel of the
+// weighted null (sq_covar_wstat_null_dev.hip); the launch site takes `total` from it and the kernel carves with it (as
+// sq_launch_lds.h does for the launched kernels).  Every offset is a multiple of 16 and the total stays below 64 KB: no limit
+// is raised.  tests/native/covar_wstat_host.cpp checks the layout and runs the header as one thread
+// (tests/native/covar_wstat_null_host.cpp: the null's kind).
 #pragma once
 #include <stddef.h>
 #include "sq_covar_stat.h"
@@ -48,15 +49,28 @@
 #define SQ_COVWSTAT_STAGE 1024
 #define SQ_COVWSTAT_EMIT_BYTES 16
 
-enum { SQ_COVWSTAT_LDS_SUMS = 0, SQ_COVWSTAT_LDS_SCAN = 1, SQ_COVWSTAT_LDS_PAIRS = 2 };
+// The thresholds (8 bytes each) and bins (4 bytes each) that the scan of the weighted null (sq_covar_wstat_null.h) keeps in LDS
+// beside the planes, q and the 32 KB of counters; thresholds and bins beyond them are global memory.  The 2048 of the
+// unweighted null (24 KB) would not fit below 64 KB here.  Measured on an MI355X (512 x 5,000, 100 samples, 433 thresholds, the
+// entry alone): 512, 768 and 896 bins 546 - 547 ms, 1024 and 1536 bins 568 - 569 ms.  With 896 a block has 52,752 bytes and a CU
+// of 160 KB holds three, the blocks the kernel's 132 registers admit; with 1024 (54,288 bytes, three of which are still below
+// 160 KB) the time is that of 1536, where two fit: presumably the LDS is handed out in units that keep the third block out
+// (supposed from these times, not read anywhere).  So 896, the most that was as fast as fewer.  (A build may set another multiple of 4 to measure it:
+// tools/covariation_wstat_null_probe.py, DESIGN.md.)
+#ifndef SQ_COVWSTATNULL_LDS_BINS
+#define SQ_COVWSTATNULL_LDS_BINS 896
+#endif
+
+enum { SQ_COVWSTAT_LDS_SUMS = 0, SQ_COVWSTAT_LDS_SCAN = 1, SQ_COVWSTAT_LDS_PAIRS = 2, SQ_COVWSTAT_LDS_NULL = 3 };
 
 // The LDS of a 256-thread block, in bytes from the start of its dynamic region.  planes: uint64 [2][4][WORD_CHUNK][TILE], the
 // planes A C G U of the tile's two column ranges; q: uint32 [64 * WORD_CHUNK], the weights of the chunk's rows; bins: int64
 // [16][256], bins[k][tid] = cell k of the table of the thread's cell (a wave's lanes hit consecutive addresses and a bin has
 // one writer).  Pass 1 then has S: double [TILE][TILE + 1] and row, col: double [TILE]; pass 2 the stage's flat: int64
-// [STAGE], raw: double [STAGE] and em (SqEmitStage).  The pairs kernel has the bins alone.  A region a kernel does not have
-// is empty, at the offset of the one after it.
-struct SqCovarWstatLds { uint32_t planes, q, bins, S, row, col, flat, raw, em; size_t total; };
+// [STAGE], raw: double [STAGE] and em (SqEmitStage).  The pairs kernel has the bins alone.  The null's scan has, after the
+// bins, thresholds: double [SQ_COVWSTATNULL_LDS_BINS], hist: uint32 [SQ_COVWSTATNULL_LDS_BINS] and top: one uint64 (the
+// block's largest key) in 16 bytes.  A region a kernel does not have is empty, at the offset of the one after it.
+struct SqCovarWstatLds { uint32_t planes, q, bins, S, row, col, flat, raw, em, thresholds, hist, top; size_t total; };
 SQ_COV_HD inline SqCovarWstatLds sq_covar_wstat_lds(int kernel)
 {
     SqCovarWstatLds L;
@@ -71,6 +85,9 @@ SQ_COV_HD inline SqCovarWstatLds sq_covar_wstat_lds(int kernel)
     L.flat = o;   o += kernel == SQ_COVWSTAT_LDS_SCAN ? SQ_COVWSTAT_STAGE * 8u : 0u;
     L.raw = o;    o += kernel == SQ_COVWSTAT_LDS_SCAN ? SQ_COVWSTAT_STAGE * 8u : 0u;
     L.em = o;     o += kernel == SQ_COVWSTAT_LDS_SCAN ? (uint32_t)SQ_COVWSTAT_EMIT_BYTES : 0u;
+    L.thresholds = o; o += kernel == SQ_COVWSTAT_LDS_NULL ? SQ_COVWSTATNULL_LDS_BINS * 8u : 0u;
+    L.hist = o;   o += kernel == SQ_COVWSTAT_LDS_NULL ? SQ_COVWSTATNULL_LDS_BINS * 4u : 0u;
+    L.top = o;    o += kernel == SQ_COVWSTAT_LDS_NULL ? 16u : 0u;
     L.total = o;
     return L;
 }

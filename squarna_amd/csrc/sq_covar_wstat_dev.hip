@@ -16,7 +16,7 @@
 // no float atomics, and the float sums have the fixed order of sq_covar_stat_dev.hip, so two calls give the same bits.  All
 // buffers are the caller's device memory, everything is enqueued on the caller's stream, nothing is allocated or waited for.
 #include "sq_host_int.h"
-#include "sq_covar_wstat.h"
+#include "sq_covar_wstat_dev.h"
 #include "sq_covar_planes.h"
 #include "sq_emit.h"
 #include <cmath>
@@ -27,59 +27,7 @@ constexpr int T = SQ_COVSTAT_TILE, CH = SQ_COVSTAT_WORD_CHUNK, PASSES = 4;
 static_assert(T == 32 && SQ_EMIT_BLOCK == 256 && 64 * CH == 256, "a tile is four cells per thread of a 256-thread block, a chunk one row per thread");
 static_assert(SQ_EMIT_STAGE == SQ_COVWSTAT_STAGE && sizeof(SqEmitStage) <= SQ_COVWSTAT_EMIT_BYTES, "sq_covar_wstat_lds() places sq_emit.h's stage");
 static_assert(sizeof(long long) == sizeof(int64_t), "the stage's flat indices");
-
-extern __shared__ __attribute__((aligned(16))) char s_dyn[];
-
-struct WstatPlanesLds {
-    uint64_t v[4][CH][T], w[4][CH][T];                              // the planes A C G U of the tile's two column ranges
-};
-
-// The 16 bins of the thread's cell (w = w0 + tid % 32, v = v0 + vl) over all rows: bins[k * 256], cleared here.  Per CH words
-// of rows the planes of both column ranges and the chunk's 256 weights are staged in LDS; words beyond W are staged as zero
-// (q is zero beyond R up to the chunk), so every trip count is block-uniform.  v0 + 31, w0 + 31 < Lpad.
-__device__ __forceinline__ void tile_bins(const uint64_t *plane, const uint32_t *q, int64_t W, int64_t Lpad, int64_t v0, int64_t w0,
-                                          WstatPlanesLds &s, uint32_t *s_q, int vl, int64_t *bins, int64_t Q[16])
-{
-    const int tid = threadIdx.x, wl = tid & 31;
-    for (int k = 0; k < 16; k++) bins[k * 256] = 0;
-    for (int64_t wb = 0; wb < W; wb += CH) {
-        __syncthreads();                                             // (the last chunk has been read)
-        for (int i = tid; i < 4 * CH * T; i += 256) {
-            const int p = i / (CH * T), wd = i / T % CH, col = i % T;
-            const bool have = wb + wd < W;
-            s.v[p][wd][col] = have ? plane[SqCovar::at(p, wb + wd, v0 + col, W, Lpad)] : 0ull;
-            s.w[p][wd][col] = have ? plane[SqCovar::at(p, wb + wd, w0 + col, W, Lpad)] : 0ull;
-        }
-        s_q[tid] = q[wb * 64 + tid];                                 // (wb * 64 + 255 < rpad(R))
-        __syncthreads();
-        for (int wd = 0; wd < CH; wd++) {
-            uint64_t a[4], b[4];
-            for (int p = 0; p < 4; p++) {
-                a[p] = s.v[p][wd][vl];
-                b[p] = s.w[p][wd][wl];
-            }
-            SqCovarWstat::accumulate(a, b, s_q + wd * 64, bins, 256);
-        }
-    }
-    for (int k = 0; k < 16; k++) Q[k] = bins[k * 256];
-}
-
-// The 16 counters of one cell from global memory, through the thread's bins (the pairs lookup, and the scan's flush for the
-// records it writes: between two cells of the walk the thread's bins are free).
-__device__ __forceinline__ void cell_bins(const uint64_t *plane, const uint32_t *q, int64_t W, int64_t Lpad, int64_t v, int64_t w,
-                                          int64_t *bins, int64_t Q[16])
-{
-    for (int k = 0; k < 16; k++) bins[k * 256] = 0;
-    for (int64_t wd = 0; wd < W; wd++) {
-        uint64_t a[4], b[4];
-        for (int p = 0; p < 4; p++) {
-            a[p] = plane[SqCovar::at(p, wd, v, W, Lpad)];
-            b[p] = plane[SqCovar::at(p, wd, w, W, Lpad)];
-        }
-        SqCovarWstat::accumulate(a, b, q + wd * 64, bins, 256);      // (wd * 64 + 63 < rpad(R))
-    }
-    for (int k = 0; k < 16; k++) Q[k] = bins[k * 256];
-}
+// (the staged planes of a tile, tile_bins() and cell_bins(): sq_covar_wstat_dev.h)
 
 }  // namespace
 
@@ -233,6 +181,24 @@ extern "C" size_t sq_covariation_wstat_scratch(int32_t R, int32_t L)
     return R < 1 || L < 1 ? 0 : (size_t)SqCovarWstat::scratch_words(R, L) * 8;
 }
 
+// The two launches the weighted null shares with the entries here (sq_covar_planes.h): q[rpad(R)] of the weights, and pass 1
+// of one alignment's planes.
+int covar_wstat_quantise(const double *d_weights, int32_t R, uint32_t *d_q, uint64_t *d_out, hipStream_t st)
+{
+    const int64_t Rpad = SqCovarWstat::rpad(R);
+    hipLaunchKernelGGL(sq_covar_wstat_quantise_kernel, dim3((unsigned)(Rpad / 256)), dim3(256), 0, st, d_weights, R, Rpad, d_q,
+                       (unsigned long long *)d_out);
+    return sq_check(hipGetLastError(), "sq_covar_wstat_quantise_kernel");
+}
+
+int covar_wstat_sums(const uint64_t *d_plane, const uint32_t *d_q, int32_t R, int32_t L, int32_t stat, double *d_partial, hipStream_t st)
+{
+    const unsigned blocks = (unsigned)std::min<int64_t>(SqCovar::tile_count(SqCovarStat::tiles(L)), SQ_COVSTAT_MAX_BLOCKS);
+    hipLaunchKernelGGL(sq_covar_wstat_sums_kernel, dim3(blocks), dim3(256), sq_covar_wstat_lds(SQ_COVWSTAT_LDS_SUMS).total, st, d_plane, d_q, R,
+                       L, stat, d_partial);
+    return sq_check(hipGetLastError(), "sq_covar_wstat_sums_kernel");
+}
+
 // The checks both entries share; then the planes and q in d_scratch and, with a correction, pass 1 and the two reductions:
 // d_mean.
 static int wstat_open(const char *who, const uint8_t *d_rows, int32_t R, int32_t L, const double *d_weights, int32_t stat, int32_t corr,
@@ -254,16 +220,10 @@ static int wstat_open(const char *who, const uint8_t *d_rows, int32_t R, int32_t
     if (int rc = covar_planes(who, d_rows, R, L, d_scratch, scratch_bytes, d_out, st)) return rc;
     const uint64_t *plane = (const uint64_t *)d_scratch;
     uint32_t *q = (uint32_t *)((uint64_t *)d_scratch + SqCovarWstat::q_at(R, L));
-    const int64_t Rpad = SqCovarWstat::rpad(R);
-    hipLaunchKernelGGL(sq_covar_wstat_quantise_kernel, dim3((unsigned)(Rpad / 256)), dim3(256), 0, st, d_weights, R, Rpad, q,
-                       (unsigned long long *)d_out);
-    if (int rc = sq_check(hipGetLastError(), "sq_covar_wstat_quantise_kernel")) return rc;
+    if (int rc = covar_wstat_quantise(d_weights, R, q, d_out, st)) return rc;
     if (corr == SQ_COVSTAT_NONE) return 0;
     double *partial = (double *)d_scratch + SqCovar::plane_words(R, L);
-    const unsigned blocks = (unsigned)std::min<int64_t>(SqCovar::tile_count(SqCovarStat::tiles(L)), SQ_COVSTAT_MAX_BLOCKS);
-    hipLaunchKernelGGL(sq_covar_wstat_sums_kernel, dim3(blocks), dim3(256), sq_covar_wstat_lds(SQ_COVWSTAT_LDS_SUMS).total, st, plane,
-                       (const uint32_t *)q, R, L, stat, partial);
-    if (int rc = sq_check(hipGetLastError(), "sq_covar_wstat_sums_kernel")) return rc;
+    if (int rc = covar_wstat_sums(plane, q, R, L, stat, partial, st)) return rc;
     return covar_stat_means(partial, L, d_mean, st);
 }
 

@@ -40,6 +40,8 @@ COVAR_NULL_BATCH_BYTES = 256 << 20
 COVAR_NULL_BATCH = 64
 #: the thresholds and bins sq_covariation_stat_null's scan keeps in LDS (SQ_COVSTATNULL_LDS_BINS, csrc/sq_covar_stat_null.h)
 COVAR_STAT_NULL_LDS_BINS = 2048
+#: the thresholds and bins sq_covariation_wstat_null's scan keeps in LDS (SQ_COVWSTATNULL_LDS_BINS, csrc/sq_covar_wstat.h)
+COVAR_WSTAT_NULL_LDS_BINS = 896
 #: sq_row_identity's tile of rows, the 64-column words it keeps in LDS at a time, the most blocks it launches, the most rows
 #: and columns it takes and the words of neighbour bits a lane of its filter kernel holds ahead (SQ_ID_TILE, SQ_ID_WORD_CHUNK, SQ_ID_MAX_BLOCKS,
 #: SQ_ID_MAX_ROWS, SQ_ID_MAX_COLS, SQ_ID_FILTER_WORDS, csrc/sq_identity.h)
@@ -516,6 +518,50 @@ class DeviceCalls:
             _result_words(out, "sq_covariation_stat_null: a pair is not 0 <= v < w < %d columns" % Lcols)
             # hist[b] = the null cells with exactly b thresholds <= their C: value[p], the t-th threshold, is reached by the bins
             # from t + 1 on
+            from_bin = torch.flip(torch.cumsum(torch.flip(hist, (0,)), 0), (0,))
+            null_ge = from_bin[torch.searchsorted(thresholds, value) + 1] if P else torch.empty(0, dtype=torch.int64, device=dev)
+        return null_ge, own_ge, null_max
+
+    def covariation_wstat_null(self, rows, weights, pairs, value, statistic="gt", correction="apc", minspan=4, samples=100, seed=0,
+                               batch=None):
+        """covariation_stat_null with a weight per row (sq_covariation_wstat_null): weights = float64 device tensor [R] as
+        covariation_wstat_scan takes them, value = the observed C of the weighted statistics.  Row r of every shuffled sample
+        keeps weights[r]: a null cell's value is what covariation_wstat_scan gives for the shuffled rows and the same weights.
+        Returns the device tensors (null_ge int64[P], own_ge int32[P], null_max float64[samples]) as covariation_stat_null does;
+        `batch` is chosen as there and the results do not depend on it.  RuntimeError for a bad weight or a bad pair.  Only the
+        two result words come to the host."""
+        import torch
+        L = _lib.load()
+        assert rows.dtype == torch.uint8 and rows.is_cuda and rows.dim() == 2 and rows.is_contiguous()
+        assert pairs.dtype == torch.int32 and pairs.dim() == 2 and int(pairs.shape[1]) == 2 and pairs.device == rows.device
+        assert value.dtype == torch.float64 and value.dim() == 1 and value.device == rows.device and int(value.numel()) == int(pairs.shape[0])
+        stat, corr = COVAR_STATISTICS.index(statistic), COVAR_CORRECTIONS.index(correction)
+        dev, R, Lcols, P, K = rows.device, int(rows.shape[0]), int(rows.shape[1]), int(pairs.shape[0]), int(samples)
+        assert weights.dtype == torch.float64 and weights.device == dev and tuple(weights.shape) == (R,) and weights.is_contiguous()
+        pairs, value = pairs.contiguous(), value.contiguous()
+        if batch is None:
+            per = int(L.sq_covariation_wstat_null_scratch(R, Lcols, 2)) - int(L.sq_covariation_wstat_null_scratch(R, Lcols, 1))
+            batch = max(1, min(K, COVAR_NULL_BATCH, COVAR_NULL_BATCH_BYTES // max(per, 1)))
+        batch = int(batch)
+        with torch.cuda.device(dev):
+            thresholds = torch.unique(value)                         # (sorted; -0.0 and 0.0 are one value)
+            U = int(thresholds.numel())
+            nbytes = int(L.sq_covariation_wstat_null_scratch(R, Lcols, batch))
+            scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+            hist = torch.empty(U + 1, dtype=torch.int64, device=dev)
+            own_ge = torch.empty(P, dtype=torch.int32, device=dev)
+            null_max = torch.empty(K, dtype=torch.float64, device=dev)
+            out = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.check(L.sq_covariation_wstat_null(_ptr(rows), R, Lcols, stat, corr, int(minspan), _ptr(pairs if P else None),
+                                                   _ptr(value if P else None), P, _ptr(thresholds if U else None), U, K, int(seed), batch,
+                                                   _ptr(scratch), nbytes, _ptr(hist), _ptr(own_ge if P else None), _ptr(null_max), _ptr(out),
+                                                   _stream(dev), _ptr(weights)))
+            status = out.tolist()[1]
+            if status == 3:
+                raise RuntimeError("sq_covariation_wstat_null: a weight is not a finite number in 0 .. 2048")
+            if status:
+                raise RuntimeError("sq_covariation_wstat_null: a pair is not 0 <= v < w < %d columns" % Lcols)
+            # (hist and null_ge: as covariation_stat_null)
             from_bin = torch.flip(torch.cumsum(torch.flip(hist, (0,)), 0), (0,))
             null_ge = from_bin[torch.searchsorted(thresholds, value) + 1] if P else torch.empty(0, dtype=torch.int64, device=dev)
         return null_ge, own_ge, null_max

@@ -688,6 +688,46 @@ SQ_API int sq_row_identity_phases(int32_t phases, const uint8_t *d_rows, int32_t
                                   void *d_scratch, size_t scratch_bytes, int32_t *d_len, int32_t *d_bases, int32_t *d_same,
                                   int32_t *d_both, int32_t *d_neighbours, uint8_t *d_keep, uint64_t *d_out, void *hip_stream);
 
+/* ---- base-pair distances, neighbour counts and the greedy filter of structures (Distances) --------------------------------
+ * S structure rows: row q is the row_width[q] partners at d_partner[row_start[q] ..] (int32[partner_len]; p[i] = the partner
+ * of column i or -1), Wmax = the widest row.  The pairs of a row are {(i, p[i]) : p[i] > i}; npairs[a] = their number,
+ * common[a, b] = the pairs rows a and b share, d(a, b) = npairs[a] + npairs[b] - 2 common[a, b].  A row is invalid (status 1,
+ * npairs 0, no cell, nobody's neighbour, neighbours 0, keep 0, leader -1) when its place is not inside d_partner, a partner
+ * lies outside [-1, width), p[p[i]] != i or p[i] == i.  Rows are compared within a group only: group g of the G groups has the
+ * consecutive rows d_group_off[g] .. d_group_off[g + 1] - 1 (int32[G + 1], from 0 to S), d_row_group[q] = the group of row q,
+ * max_group_rows = the rows of the largest.  Rows a != b of one group are neighbours iff d <= threshold (mode 0, a radius >= 0)
+ * or d * 10000 <= threshold * (npairs[a] + npairs[b]) (mode 1, basis points 0..10000), in int64.  d_tiles int32[T * 2] = the
+ * planned tiles (ta, tb) of 64 x 64 rows: the upper-triangle tiles over the global row index that hold a cell of one group
+ * (SqDistances::plan_tiles, csrc/sq_distances.h).
+ * Outputs: d_status, d_npairs, d_neighbours (1 + the neighbours of a), d_leader int32[S], d_keep uint8[S] (greedy in row
+ * order within the group: row a is kept iff no kept row below it in its group is its neighbour; leader = the row itself
+ * when kept, else its lowest kept neighbour, a global row index), and d_common int32[common_cells], which may be null with
+ * common_cells 0: the cell (a, b) of group g of n_g rows sits at d_mat_off[g] + (a - first) * n_g + (b - first) (int64[G + 1]).
+ * d_out[0] = 0; d_out[1] = a status: bit 0 an entry of d_tiles outside the tile range (skipped), bit 1 a group the filter
+ * could not take (offsets not ascending within 0..S, or more rows than max_group_rows says; left alone).
+ * d_scratch (sq_structure_distances_scratch(S, Wmax, T) bytes, 8-byte aligned; 0 for sizes the entry refuses) holds the rows
+ * as 1 + bits(Wmax - 1) bit planes of 64 columns per word and the neighbour bit matrix uint64[S * ceil(S / 64)].  Three kernels,
+ * one after the other: the planes, the planned tiles from LDS, the filter with one wave per group.
+ * Asynchronous on hip_stream, allocates nothing; 0, or -1 (a null pointer other than d_common, d_common without cells or
+ * cells without it, S < 1, S above 65535, Wmax < 1, Wmax above 32768, partner_len < 1, G < 1, max_group_rows outside 1..S,
+ * T < 1 or above the upper triangle's tiles, a mode outside 0..1, a threshold < 0 or above 10000 basis points, scratch too
+ * small: nothing enqueued, nothing written).
+ * sq_structure_distances_phases: the same call with only the kernels of `phases` (bit 0: the planes with status and npairs,
+ * bit 1: the pairs, bit 2: the filter; 1..7, else -1) on buffers that hold what the earlier phases left. */
+SQ_API size_t sq_structure_distances_scratch(int32_t S, int32_t Wmax, int32_t T);
+SQ_API int sq_structure_distances(const int32_t *d_partner, int64_t partner_len, const int64_t *d_row_start, const int32_t *d_row_width,
+                                  const int32_t *d_row_group, int32_t S, int32_t Wmax, const int32_t *d_group_off, const int64_t *d_mat_off,
+                                  int32_t G, int32_t max_group_rows, const int32_t *d_tiles, int32_t T, int32_t mode, int32_t threshold,
+                                  void *d_scratch, size_t scratch_bytes, int32_t *d_status, int32_t *d_npairs, int32_t *d_common,
+                                  int64_t common_cells, int32_t *d_neighbours, int32_t *d_leader, uint8_t *d_keep, uint64_t *d_out,
+                                  void *hip_stream);
+SQ_API int sq_structure_distances_phases(int32_t phases, const int32_t *d_partner, int64_t partner_len, const int64_t *d_row_start,
+                                         const int32_t *d_row_width, const int32_t *d_row_group, int32_t S, int32_t Wmax,
+                                         const int32_t *d_group_off, const int64_t *d_mat_off, int32_t G, int32_t max_group_rows,
+                                         const int32_t *d_tiles, int32_t T, int32_t mode, int32_t threshold, void *d_scratch,
+                                         size_t scratch_bytes, int32_t *d_status, int32_t *d_npairs, int32_t *d_common, int64_t common_cells,
+                                         int32_t *d_neighbours, int32_t *d_leader, uint8_t *d_keep, uint64_t *d_out, void *hip_stream);
+
 /* ---- measurement ------------------------------------------------------------
  * Kernel ids: 0 fill, 1 state, 2 stem_scan, 3 stem_score (+ select), 4 Edmonds, 5 Hungarian,
  * 6 Nussinov, 9 the bpp terms formed at sq_batch_create from bpp_matrix_dev (both kernels; recorded whether profiling

@@ -53,6 +53,19 @@ IDENTITY_MAX_COLS = 1 << 21
 IDENTITY_FILTER_WORDS = 64
 #: the denominators of sq_row_identity by name (SQ_ID_DEN_*, csrc/sq_identity.h)
 IDENTITY_DENOMINATORS = ("shorter", "aligned", "columns")
+#: sq_structure_distances' tile of rows, the 64-column words it keeps in LDS at a time, the most blocks it launches, the most
+#: rows, columns and planes it takes and the words of neighbour bits a lane of its filter kernel holds ahead (SQ_DIST_TILE,
+#: SQ_DIST_WORD_CHUNK, SQ_DIST_MAX_BLOCKS, SQ_DIST_MAX_ROWS, SQ_DIST_MAX_COLS, SQ_DIST_MAX_PLANES, SQ_DIST_FILTER_WORDS,
+#: csrc/sq_distances.h)
+DISTANCES_TILE = 64
+DISTANCES_WORD_CHUNK = 2
+DISTANCES_MAX_BLOCKS = 2048
+DISTANCES_MAX_ROWS = 65535
+DISTANCES_MAX_COLS = 32768
+DISTANCES_MAX_PLANES = 16
+DISTANCES_FILTER_WORDS = 64
+#: the neighbour tests of sq_structure_distances by name (SQ_DIST_RADIUS, SQ_DIST_RELATIVE, csrc/sq_distances.h)
+DISTANCES_MODES = ("radius", "relative")
 #: the rows (waves) of a block of sq_elements_rows' loops kernel (SQ_ELEM_WAVES, csrc/sq_elements.h)
 ELEMENTS_WAVES = 4
 #: the stems and the pseudoknot levels of a row beyond which sq_elements_rows leaves it to the host (SQ_CHAIN_TMAX,
@@ -587,6 +600,43 @@ class DeviceCalls:
                                          _ptr(res["bases"]), _ptr(res["same"]), _ptr(res["both"]), _ptr(res["neighbours"]),
                                          _ptr(res["keep"]), _ptr(out), _stream(dev)))
             _result_words(out, "sq_row_identity: status")            # (the entry has no status: out[1] stays 0)
+        res["keep"] = res["keep"].bool()
+        return res
+
+    def structure_distances(self, partner, row_start, row_width, group_off, tiles, mode=0, threshold=0, matrix=True):
+        """Base-pair distances, neighbour counts and the greedy filter of structure rows, on the device
+        (sq_structure_distances): partner = a flat int32 CUDA tensor of partner rows, read where it is; the small tables are
+        host arrays and go up in one copy: row_start / row_width = per row where it starts in partner and its columns,
+        group_off [G + 1] = the groups' first rows (from 0 to S), tiles [T, 2] = the planned tiles (distances.plan_tiles).
+        mode = 0 / 1 (DISTANCES_MODES: a radius in pairs, basis points of the relative distance) and its threshold.  Returns a
+        dict of device tensors: status, npairs, neighbours, leader int32[S], keep bool[S] and common (with `matrix`: the
+        block-diagonal int32 matrix of the groups, flat, group g's cells from sum of n^2 of the groups before it on; else
+        None: then nothing of that size is written).  Only the two result words come to the host."""
+        import torch
+        L = _lib.load()
+        dev = partner.device
+        assert partner.is_cuda and partner.dtype == torch.int32 and partner.dim() == 1 and partner.is_contiguous()
+        row_start, row_width = np.asarray(row_start, np.int64), np.asarray(row_width, np.int32)
+        group_off, tiles = np.asarray(group_off, np.int32), np.ascontiguousarray(tiles, np.int32).reshape(-1, 2)
+        S, G, T = len(row_start), len(group_off) - 1, len(tiles)
+        n = np.diff(group_off.astype(np.int64))
+        assert len(row_width) == S and G >= 1 and group_off[0] == 0 and group_off[-1] == S and (n >= 0).all()
+        mat_off = offsets(n * n)
+        cells, Wmax = int(mat_off[-1]) if matrix else 0, int(row_width.max())
+        with torch.cuda.device(dev):
+            d_start, d_width, d_group, d_goff, d_moff, d_tiles = _upload_once(
+                [row_start, row_width, np.repeat(np.arange(G, dtype=np.int32), n), group_off, mat_off, tiles], dev)
+            nbytes = int(L.sq_structure_distances_scratch(S, Wmax, T))
+            scratch = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            res = dict(status=new(S, torch.int32), npairs=new(S, torch.int32), neighbours=new(S, torch.int32), leader=new(S, torch.int32),
+                       keep=new(S, torch.uint8), common=new(cells, torch.int32) if matrix else None)
+            out = torch.empty(2, dtype=torch.int64, device=dev)
+            _lib.check(L.sq_structure_distances(_ptr(partner), int(partner.numel()), _ptr(d_start), _ptr(d_width), _ptr(d_group), S, Wmax,
+                                                _ptr(d_goff), _ptr(d_moff), G, int(n.max()), _ptr(d_tiles), T, int(mode), int(threshold),
+                                                _ptr(scratch), nbytes, _ptr(res["status"]), _ptr(res["npairs"]), _ptr(res["common"]), cells,
+                                                _ptr(res["neighbours"]), _ptr(res["leader"]), _ptr(res["keep"]), _ptr(out), _stream(dev)))
+            _result_words(out, "sq_structure_distances: a tile or a group outside the rows")
         res["keep"] = res["keep"].bool()
         return res
 

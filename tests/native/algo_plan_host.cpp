@@ -1,7 +1,10 @@
 // Test-only host harness of the plan of a matching chunk (squarna_amd/csrc/sq_algo_plan.h), compiled without HIP.
 //   no argument: stdin holds cases, one per line; stdout gets one JSON object per case with the keys of tests/golden/algo_plan.json.gz
 //     C algo inflight region_bytes dev lsap_classes mwm_classes nj  n ncell  n ncell ...      (a chunk)
-//     M inflight bin_waves bin_bytes all_cap nolds nj  n m  n m ...                          (the LDS bins of one blossom launch)
+//     M inflight bin_waves bin_bytes all_cap nolds nj  n m  n m ...                          (the LDS bins of one blossom launch,
+//                                                                                             "hdr" and the kernel's "forms" besides)
+//     N inflight nuss_threads nj  n m  n m ...                                               (the block size of one Nussinov launch)
+//     S n m                                                                                   (the sizes of one graph's blossom state)
 //   "props": the layout and ordering properties on synthetic job lists; prints the number of plans checked, exit 1 on a failure.
 #include <cstdio>
 #include <cstdlib>
@@ -62,7 +65,37 @@ static int replay()
             for (int q = 0; q < nj; q++) printf("%s[%d,%d,%d]", q ? "," : "", rw[q].lds_off, rw[q].lds_bytes, rw[q].next);
             printf("],\"bin_head\":[");
             for (int k = 0; k < M.nbins; k++) printf("%s%d", k ? "," : "", head[k]);
+            // the storage form the KERNEL takes for every graph (the two tests at the top of sq_mwm_one; -1: no vertex): a
+            // one-graph block sees the launch-wide LDS less the algorithm object, a wave of a bin its own slice less the object
+            const size_t hdr = sq_blossom_hdr();
+            printf("],\"hdr\":%zu,\"forms\":[", hdr);
+            for (int q = 0; q < nj; q++) {
+                const int n = jobs[q].n, m = jobs[q].nedges;
+                const size_t have = M.waves == 1 ? M.lds : (size_t)rw[q].lds_bytes;
+                const size_t lds_bytes = have > hdr ? have - hdr : 0;
+                const size_t ebytes = ((size_t)m * sizeof(SqMatchEdge) + 15) & ~(size_t)15;
+                int form = 0;
+                if (n <= 0) form = -1;
+                else if (SqBlossom::scratch_bytes(n, m, 1) + ebytes + 16 <= lds_bytes) form = 1;
+                else if (SqBlossom::hot_bytes(n, m, 2) + 16 <= lds_bytes) form = 2;
+                printf("%s%d", q ? "," : "", form);
+            }
             printf("]}\n");
+        } else if (kind == 'N') {
+            int inflight, nj, maxn = 0;
+            SqAlgoKnobs kn;
+            if (scanf("%d %d %d", &inflight, &kn.nuss_threads, &nj) != 3) return 1;
+            std::vector<SqMatchJob> jobs((size_t)nj);
+            for (auto &J : jobs) { J = SqMatchJob(); if (scanf("%d %d", &J.n, &J.nedges) != 2) return 1; maxn = std::max(maxn, (int)J.n); }
+            printf("{\"threads\":%d}\n", sq_nussinov_threads(jobs.data(), nj, maxn, inflight, kn));
+        } else if (kind == 'S') {
+            int n, m;
+            if (scanf("%d %d", &n, &m) != 2) return 1;
+            printf("{\"hdr\":%zu,\"edge\":%zu", sq_blossom_hdr(), SqBlossom::edge_bytes(m));
+            for (int t = 0; t < 3; t++)
+                printf(",\"t%d\":[%zu,%zu,%zu,%d,%d,%d]", t, SqBlossom::hot_bytes(n, m, t), SqBlossom::cold_bytes(n, m, t), SqBlossom::scratch_bytes(n, m, t),
+                       t == 2 ? SqBlossom::queue_hot_cap(n) : SqBlossom::queue_cap(n, m, t), SqBlossom::pool_capacity(n, m, t ? 1 : 0), SqBlossom::frame_ints(n, t ? 1 : 0));
+            printf("}\n");
         } else return 1;
     }
     return 0;

@@ -19,23 +19,12 @@ def _once(key, make):
 
 
 # ------------------------------------------------------------------ sq_nussinov
-#: the early return (0, 1), the first cell that can exist (5), one wave, one 256-thread block, rows that stride it
-NUSS_SIZES = (0, 1, 2, 4, 5, 6, 63, 64, 65, 128, 129, 256, 257, 300)
+NUSS_SIZES = M.NUSS_SIZES
 
 
 def _nussinov_problems():
     def make():
-        import numpy as np
-        probs = []
-        for t, n in enumerate(NUSS_SIZES):
-            for d, dens in enumerate((0.0, 0.4, 1.5, 3.0)):
-                if n < 5 and d > 1:
-                    continue                                 # no cell fits: the empty problem once, and once asked for cells
-                probs.append(M.nussinov_case(3000 + 10 * t + d, n, int(dens * n), (M.DYADIC + (M.DYADIC[2],))[(t + d) % 4]))
-        for t, n in enumerate((6, 65, 129, 257)):            # separators: BackTrack's other branch, cells of span 2 and 3
-            probs.append(M.nussinov_case(3500 + t, n, 2 * n, M.DYADIC[1], seps=True))
-        order = np.random.default_rng(31).permutation(len(probs))
-        probs = [probs[int(t)] for t in order]
+        probs = M.nussinov_problem_set()                     # (shared with tests/test_hip_matching_forms.py)
         exp = [M.oracle_nussinov(seq, cells) for seq, cells in probs]
         for (seq, cells), pairs in zip(probs, exp):          # the reference itself is an optimum (test_matching_reference.py)
             if ";" not in seq and "&" not in seq:

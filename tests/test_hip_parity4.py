@@ -335,8 +335,9 @@ def test_blossom_large_graphs_hubs_and_stars_match_networkx():
     import random
     import networkx as nx
     import squarna_amd as S
+    from tests.matching_checks import mwm_dims, mwm_launch
     rng = random.Random(20261004)
-    cases = []
+    cases, forms = [], []
     for trial in range(10):
         n = rng.randrange(200, 600)
         deg = rng.choice((2, 3, 5, 8))
@@ -362,6 +363,10 @@ def test_blossom_large_graphs_hubs_and_stars_match_networkx():
         exp = sorted(nx.max_weight_matching(G))
         got = S.Edmonds([[[(u, v)], 1, w] for u, v, w in edges], power=1.0)
         assert got == exp, (k, n, len(edges))
+        forms += mwm_launch([mwm_dims(edges)])["forms"]
+    # one graph per call, a block of 150 KB: the graphs of 465, 554, 435 and 585 vertices keep only the hot part of their state
+    # in LDS, the others all of it (tests/test_hip_matching_forms.py has every form in both kernels)
+    assert forms == [1, 1, 2, 1, 1, 2, 1, 1, 2, 2, 1, 1, 1]
 
 
 def _packed(b, n):

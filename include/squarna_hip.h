@@ -728,6 +728,38 @@ SQ_API int sq_structure_distances_phases(int32_t phases, const int32_t *d_partne
                                          size_t scratch_bytes, int32_t *d_status, int32_t *d_npairs, int32_t *d_common, int64_t common_cells,
                                          int32_t *d_neighbours, int32_t *d_leader, uint8_t *d_keep, uint64_t *d_out, void *hip_stream);
 
+/* ---- structures between the columns of an alignment and the residues of its rows (Project, Lift) ---------------------------
+ * d_rows = uint8[R * L], the rows' ASCII bytes (classes as in sq_covariation_scan: A C G U in either case, T as U, gaps
+ * - . ~, anything else "other"; a residue is any non-gap).  For every row: d_length int32[R] = its residues, d_col_of
+ * int32[R * Lmax] = the column of residue i (-1 beyond the row's length), d_pos_of int32[R * L] = the residue of column c
+ * (-1 at a gap).  Lmax >= the residues of every row is the caller's to know; a row with more gets status 2 on every line,
+ * the first Lmax entries of col_of, and no structure.
+ * sq_project_rows: K structure lines over the L columns per row, partners int32 (-1 unpaired): line k of row r at
+ * d_structs[r * row_stride + k * L ..], row_stride = 0 (the K lines are shared by all rows) or K * L.  Per (row, line):
+ * d_partner int32[R * K * Lmax] = the line in the row's residue coordinates (-1 unpaired and beyond the length), d_cls
+ * uint8[R * K * L] = at the opening column v of every pair (v, w), v < w, its class in that row (1..6 = AU UA GC CG GU UG as
+ * (letter at v, letter at w), 7 = two residues that are no canonical pair, 8 = a gap in exactly one column, 9 = a gap in
+ * both; 0 elsewhere), d_counts int32[R * K * 12] = [0] the pairs, [1..9] per class, [10] those of an admitted class that
+ * min_loop alone drops, [11] the pairs kept, d_status int32[R * K].  A pair is kept iff its class is 1..6, or 7 unless
+ * canonical_only, and at least min_loop residues of the row lie strictly between its ends.  A line with a partner outside
+ * [-1, L), p[p[c]] != c or p[c] == c has status 1, partners -1, classes and counts 0.
+ * sq_lift_rows: per row up to K structure lines over the row's residues: line k < d_nstruct[r] (int32[R], taken within
+ * 0..K) at d_short[d_start[r] + k * d_stride[r] ..] (int32[short_len]; d_start int64[R], d_stride int32[R] >= the row's
+ * length), of which the row's length first entries are read.  d_partner int32[R * K * L] = the line over the columns (-1
+ * at gaps, unpaired, and on the lines beyond d_nstruct[r], whose status is 0), d_status int32[R * K]: 1 for a line that is
+ * invalid against the row's length, 2 for a row whose lines do not lie inside d_short or are narrower than its length.
+ * One kernel each, a block per row at a time with the row's gap map in LDS as 64-column ballot words (csrc/sq_project.h);
+ * every output cell is written by the kernel.  Asynchronous on hip_stream, allocate nothing, need no scratch; 0, or -1 (a
+ * null pointer, R outside 1..2^20, L or Lmax outside 1..32768, K < 1, a row_stride other than 0 and K * L, canonical_only
+ * outside 0..1, a negative min_loop, short_len < 1: nothing enqueued, nothing written). */
+SQ_API int sq_project_rows(const uint8_t *d_rows, int32_t R, int32_t L, const int32_t *d_structs, int64_t row_stride, int32_t K,
+                           int32_t Lmax, int32_t canonical_only, int32_t min_loop, int32_t *d_length, int32_t *d_col_of,
+                           int32_t *d_pos_of, int32_t *d_partner, uint8_t *d_cls, int32_t *d_counts, int32_t *d_status,
+                           void *hip_stream);
+SQ_API int sq_lift_rows(const uint8_t *d_rows, int32_t R, int32_t L, const int32_t *d_short, int64_t short_len, const int64_t *d_start,
+                        const int32_t *d_stride, const int32_t *d_nstruct, int32_t K, int32_t Lmax, int32_t *d_length,
+                        int32_t *d_col_of, int32_t *d_pos_of, int32_t *d_partner, int32_t *d_status, void *hip_stream);
+
 /* ---- measurement ------------------------------------------------------------
  * Kernel ids: 0 fill, 1 state, 2 stem_scan, 3 stem_score (+ select), 4 Edmonds, 5 Hungarian,
  * 6 Nussinov, 9 the bpp terms formed at sq_batch_create from bpp_matrix_dev (both kernels; recorded whether profiling

@@ -29,6 +29,7 @@ from .covariation_statistics_significance import CovariationStatisticsSignifican
 from .elements import Elements, ElementsResult  # noqa: F401,E402
 from .row_identity import RowIdentity, IdentityResult  # noqa: F401,E402
 from .distances import Distances, DistancesResult  # noqa: F401,E402
+from .project import Project, ProjectResult, Lift, LiftResult  # noqa: F401,E402
 from .core import (BPMatrix, AnnotateStems, OptimalStems, RunAlgo, Edmonds, Hungarian, Nussinov,  # noqa: F401,E402
                    SQRNdbnseq, RunSQRNdbnseq, ScoreStruct, ReferenceScores)
 
@@ -39,5 +40,5 @@ def BuildRfam(*args, **kwargs):
     raise NotImplementedError("BuildRfam is out of scope of squarna_amd (see DESIGN.md)")
 
 
-__all__ = ["Predict", "Main", "Fold", "FoldResult", "FoldAlignment", "AlignmentResult", "Score", "ScoreResult", "Entropy", "EntropyResult", "FoldWindows", "WindowResult", "FoldMutants", "MutantResult", "FoldDuplex", "DuplexResult", "Covariation", "CovariationResult", "CovariationSignificance", "SignificanceResult", "CovariationStatistics", "CovariationStatisticsResult", "CovariationStatisticsSignificance", "StatisticsSignificanceResult", "Elements", "ElementsResult", "RowIdentity", "IdentityResult", "Distances", "DistancesResult", "BuildRfam", "ParseConfig", "BPMatrix", "AnnotateStems", "OptimalStems", "RunAlgo",
+__all__ = ["Predict", "Main", "Fold", "FoldResult", "FoldAlignment", "AlignmentResult", "Score", "ScoreResult", "Entropy", "EntropyResult", "FoldWindows", "WindowResult", "FoldMutants", "MutantResult", "FoldDuplex", "DuplexResult", "Covariation", "CovariationResult", "CovariationSignificance", "SignificanceResult", "CovariationStatistics", "CovariationStatisticsResult", "CovariationStatisticsSignificance", "StatisticsSignificanceResult", "Elements", "ElementsResult", "RowIdentity", "IdentityResult", "Distances", "DistancesResult", "Project", "ProjectResult", "Lift", "LiftResult", "BuildRfam", "ParseConfig", "BPMatrix", "AnnotateStems", "OptimalStems", "RunAlgo",
            "Edmonds", "Hungarian", "Nussinov", "SQRNdbnseq", "RunSQRNdbnseq"]

@@ -31,7 +31,7 @@ SYMBOLS = ["sq_version", "sq_last_error", "sq_last_capacity", "sq_batch_workspac
            "sq_covariation_wstat_pairs", "sq_covariation_null_scratch", "sq_covariation_null",
            "sq_covariation_null_planes", "sq_covariation_stat_null_scratch", "sq_covariation_stat_null", "sq_covariation_wstat_null_scratch",
            "sq_covariation_wstat_null", "sq_elements_scratch", "sq_elements_rows", "sq_row_identity_scratch", "sq_row_identity", "sq_row_identity_phases",
-           "sq_structure_distances_scratch", "sq_structure_distances", "sq_structure_distances_phases"]
+           "sq_structure_distances_scratch", "sq_structure_distances", "sq_structure_distances_phases", "sq_project_rows", "sq_lift_rows"]
 
 BATCH_NO_FP32 = 1
 BATCH_POOL_LISTS = 2
@@ -260,6 +260,10 @@ def load():
                                          C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sq_structure_distances_phases.argtypes = [C.c_int32] + L.sq_structure_distances.argtypes
+    L.sq_project_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sq_lift_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sq_score_scratch.restype = C.c_size_t
     L.sq_score_scratch.argtypes = [C.c_int32]
     L.sq_score_structs_dev.argtypes = [C.POINTER(ScoreDesc), C.POINTER(ScoreRows), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]

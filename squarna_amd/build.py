@@ -7,7 +7,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsquarna_hip.so")
-SOURCES = ["sq_kernels.hip", "sq_host.hip", "sq_batch.hip", "sq_round_host.hip", "sq_fold.hip", "sq_fold_chain.hip", "sq_fold_pool.hip", "sq_switches.cpp", "sq_results.hip", "sq_tail.cpp", "sq_match.hip", "sq_algos.hip", "sq_graph.hip", "sq_chain.hip", "sq_pool.hip", "sq_gather.hip", "sq_tail_dev.hip", "sq_algos_dev.hip", "sq_text.cpp", "sq_parse.cpp", "sq_context.hip", "sq_rounds.hip", "sq_pool_round.hip", "sq_align_dev.hip", "sq_bpp_dev.hip", "sq_score_dev.hip", "sq_entropy_dev.hip", "sq_window_dev.hip", "sq_variant_dev.hip", "sq_duplex_dev.hip", "sq_covar_dev.hip", "sq_covar_null_dev.hip", "sq_covar_stat_dev.hip", "sq_covar_wstat_dev.hip", "sq_covar_wstat_null_dev.hip", "sq_elements_dev.hip", "sq_identity_dev.hip", "sq_distances_dev.hip"]
+SOURCES = ["sq_kernels.hip", "sq_host.hip", "sq_batch.hip", "sq_round_host.hip", "sq_fold.hip", "sq_fold_chain.hip", "sq_fold_pool.hip", "sq_switches.cpp", "sq_results.hip", "sq_tail.cpp", "sq_match.hip", "sq_algos.hip", "sq_graph.hip", "sq_chain.hip", "sq_pool.hip", "sq_gather.hip", "sq_tail_dev.hip", "sq_algos_dev.hip", "sq_text.cpp", "sq_parse.cpp", "sq_context.hip", "sq_rounds.hip", "sq_pool_round.hip", "sq_align_dev.hip", "sq_bpp_dev.hip", "sq_score_dev.hip", "sq_entropy_dev.hip", "sq_window_dev.hip", "sq_variant_dev.hip", "sq_duplex_dev.hip", "sq_covar_dev.hip", "sq_covar_null_dev.hip", "sq_covar_stat_dev.hip", "sq_covar_wstat_dev.hip", "sq_covar_wstat_null_dev.hip", "sq_elements_dev.hip", "sq_identity_dev.hip", "sq_distances_dev.hip", "sq_project_dev.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result", "-x", "hip"]
 

@@ -66,6 +66,15 @@ DISTANCES_MAX_PLANES = 16
 DISTANCES_FILTER_WORDS = 64
 #: the neighbour tests of sq_structure_distances by name (SQ_DIST_RADIUS, SQ_DIST_RELATIVE, csrc/sq_distances.h)
 DISTANCES_MODES = ("radius", "relative")
+#: sq_project_rows / sq_lift_rows: the threads of a block (one block per alignment row at a time), the most blocks launched,
+#: the most columns and rows, the 64-column words of the longest row and the counters of a line (SQ_PROJ_THREADS,
+#: SQ_PROJ_MAX_BLOCKS, SQ_PROJ_MAX_COLS, SQ_PROJ_MAX_ROWS, SQ_PROJ_MAX_WORDS, SQ_PROJ_COUNTS, csrc/sq_project.h)
+PROJECT_THREADS = 256
+PROJECT_MAX_BLOCKS = 2048
+PROJECT_MAX_COLS = 32768
+PROJECT_MAX_ROWS = 1 << 20
+PROJECT_MAX_WORDS = 512
+PROJECT_COUNTS = 12
 #: the rows (waves) of a block of sq_elements_rows' loops kernel (SQ_ELEM_WAVES, csrc/sq_elements.h)
 ELEMENTS_WAVES = 4
 #: the stems and the pseudoknot levels of a row beyond which sq_elements_rows leaves it to the host (SQ_CHAIN_TMAX,
@@ -638,6 +647,52 @@ class DeviceCalls:
                                                 _ptr(res["neighbours"]), _ptr(res["leader"]), _ptr(res["keep"]), _ptr(out), _stream(dev)))
             _result_words(out, "sq_structure_distances: a tile or a group outside the rows")
         res["keep"] = res["keep"].bool()
+        return res
+
+    def project_rows(self, rows, structs, shared, Lmax, canonical_only=False, min_loop=0):
+        """Structure lines over the columns of an alignment projected onto the residues of its rows, on the device
+        (sq_project_rows): rows = uint8 device tensor [R, L] of the rows' ASCII bytes; structs = int32 device tensor of
+        partners, [K, L] when `shared` (read by every row where it is) else [R, K, L]; Lmax >= the residues of every row.
+        Returns a dict of device tensors: length int32[R], col_of int32[R, Lmax], pos_of int32[R, L], partner int32[R, K, Lmax],
+        cls uint8[R, K, L], counts int32[R, K, 12], status int32[R, K].  Nothing comes to the host."""
+        import torch
+        L = _lib.load()
+        assert rows.dtype == torch.uint8 and rows.is_cuda and rows.dim() == 2 and rows.is_contiguous()
+        dev, R, Lcols = rows.device, int(rows.shape[0]), int(rows.shape[1])
+        assert structs.dtype == torch.int32 and structs.device == dev and structs.is_contiguous()
+        assert tuple(structs.shape[-1:]) == (Lcols,) and structs.dim() == (2 if shared else 3) and (shared or int(structs.shape[0]) == R)
+        K, Lmax = int(structs.shape[-2]), int(Lmax)
+        with torch.cuda.device(dev):
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            res = dict(length=new(R, torch.int32), col_of=new((R, Lmax), torch.int32), pos_of=new((R, Lcols), torch.int32),
+                       partner=new((R, K, Lmax), torch.int32), cls=new((R, K, Lcols), torch.uint8),
+                       counts=new((R, K, PROJECT_COUNTS), torch.int32), status=new((R, K), torch.int32))
+            _lib.check(L.sq_project_rows(_ptr(rows), R, Lcols, _ptr(structs), 0 if shared else K * Lcols, K, Lmax, int(bool(canonical_only)),
+                                         int(min_loop), _ptr(res["length"]), _ptr(res["col_of"]), _ptr(res["pos_of"]), _ptr(res["partner"]),
+                                         _ptr(res["cls"]), _ptr(res["counts"]), _ptr(res["status"]), _stream(dev)))
+        return res
+
+    def lift_rows(self, rows, short, start, stride, nstruct, K, Lmax):
+        """Structure lines over the residues of the rows of an alignment lifted onto its columns, on the device
+        (sq_lift_rows): rows = uint8 device tensor [R, L]; short = a flat int32 device tensor of partners in residue
+        coordinates, read where it is; the small tables are host arrays and go up in one copy: line k < nstruct[r] of row r
+        starts at short[start[r] + k * stride[r]].  Returns a dict of device tensors: length int32[R], col_of int32[R, Lmax],
+        pos_of int32[R, L], partner int32[R, K, L], status int32[R, K], nstruct int32[R].  Nothing comes to the host."""
+        import torch
+        L = _lib.load()
+        assert rows.dtype == torch.uint8 and rows.is_cuda and rows.dim() == 2 and rows.is_contiguous()
+        dev, R, Lcols, K, Lmax = rows.device, int(rows.shape[0]), int(rows.shape[1]), int(K), int(Lmax)
+        assert short.dtype == torch.int32 and short.device == dev and short.dim() == 1 and short.is_contiguous()
+        start, stride, nstruct = np.asarray(start, np.int64), np.asarray(stride, np.int32), np.asarray(nstruct, np.int32)
+        assert start.shape == stride.shape == nstruct.shape == (R,)
+        with torch.cuda.device(dev):
+            d_start, d_stride, d_nstruct = _upload_once([start, stride, nstruct], dev)
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            res = dict(length=new(R, torch.int32), col_of=new((R, Lmax), torch.int32), pos_of=new((R, Lcols), torch.int32),
+                       partner=new((R, K, Lcols), torch.int32), status=new((R, K), torch.int32), nstruct=d_nstruct)
+            _lib.check(L.sq_lift_rows(_ptr(rows), R, Lcols, _ptr(short), int(short.numel()), _ptr(d_start), _ptr(d_stride), _ptr(d_nstruct), K,
+                                      Lmax, _ptr(res["length"]), _ptr(res["col_of"]), _ptr(res["pos_of"]), _ptr(res["partner"]),
+                                      _ptr(res["status"]), _stream(dev)))
         return res
 
     def score_tensors(self, recs, partner, row_start, row_rec):

@@ -76,6 +76,72 @@ def fold_result_form(cs, device=None):
     return FoldResult([">" + c["name"] for c in cs], [c["seq"] for c in cs], [[] for _ in cs], tables, nstruct, lengths, "host")
 
 
+#: the sweep of the metric ratios: the sizes of the known structures, one 200-nt record each; the pairs are (q, 199 - q)
+SWEEP_KNOWN = (0, 1, 3, 16, 48, 80)
+SWEEP_N = 200
+_sweep = None
+
+
+def sweep_counts():
+    """(K, TP, FP) of every row of the sweep, in the order of its rows: per known size K, TP = 0 .. K of the known pairs and
+    FP = 0 .. min(96, 100 - K) of the pairs beyond them."""
+    return [(K, tp, fp) for K in SWEEP_KNOWN for tp in range(K + 1) for fp in range(min(96, SWEEP_N // 2 - K) + 1)]
+
+
+def sweep_ratios(K, tp, fp):
+    """{column of the metrics: (numerator, denominator)} of the ratios a row forms (SQRNdbnali.py:205-207); none where the
+    denominator is empty."""
+    fn = K - tp
+    out = {3: (2 * tp, 2 * tp + fp + fn), 4: (tp, tp + fp), 5: (tp, tp + fn)}
+    return {k: r for k, r in out.items() if r[1]}
+
+
+def sweep_metrics(K, tp, fp):
+    """TP FP FN FS PR RC of a row in plain Python, as the reference's Metrics forms them."""
+    ratios = sweep_ratios(K, tp, fp)
+    return [tp, fp, K - tp] + [round(ratios[k][0] / ratios[k][1], 3) if k in ratios else 1 for k in (3, 4, 5)]
+
+
+def round3_floor(x):
+    """A wrong round(x, 3): half up on the product."""
+    import math
+    return math.floor(1000 * x + 0.5) / 1000
+
+
+def round3_product(x):
+    """A wrong round(x, 3): ties to even on the ROUNDED product 1000 x, not on the exact binary value."""
+    return round(1000 * x) / 1000
+
+
+def sweep_telling(wrong):
+    """The distinct (numerator, denominator) among the sweep's ratios on which `wrong` differs from round(x, 3)."""
+    seen = {r for row in sweep_counts() for r in sweep_ratios(*row).values()}
+    return {r for r in seen if wrong(r[0] / r[1]) != round(r[0] / r[1], 3)}
+
+
+def sweep():
+    """(records, int32[6, Kmax, 200] padded partner rows, nstruct, expected float64[rows, 6]) of the sweep, built once and
+    left unchanged.  Record r's known structure holds the pairs (q, 199 - q), q < SWEEP_KNOWN[r]; a row holds the first TP of
+    them and the FP pairs q = K .. K + FP - 1."""
+    global _sweep
+    if _sweep is None:
+        rng = np.random.default_rng(200)
+        n, counts = SWEEP_N, sweep_counts()
+        nstruct = np.array([sum(1 for c in counts if c[0] == K) for K in SWEEP_KNOWN], np.int64)
+        rows = np.full((len(SWEEP_KNOWN), int(nstruct.max()), n), -1, np.int32)
+        recs = []
+        for r, K in enumerate(SWEEP_KNOWN):
+            tp = np.array([c[1] for c in counts if c[0] == K])
+            fp = np.array([c[2] for c in counts if c[0] == K])
+            block = rows[r, :len(tp)]
+            for q in range(n // 2):
+                held = (q < tp) | ((q >= K) & (q < K + fp))
+                block[held, q], block[held, n - 1 - q] = n - 1 - q, q
+            recs.append((">sweep_%d" % K, ''.join(rng.choice(list("ACGU"), n)), None, None, "(" * K + "." * (n - 2 * K) + ")" * K))
+        _sweep = (recs, rows, nstruct, np.array([sweep_metrics(*c) for c in counts], np.float64))
+    return _sweep
+
+
 def same(a, b):
     """Equal as float64 values, NaN equal to NaN."""
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)

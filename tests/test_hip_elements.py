@@ -109,6 +109,26 @@ def test_mixed_records_in_one_call(kernel_calls):
     _none_handed_back(kernel_calls, (res,))
 
 
+def test_stems_at_the_chunk_boundaries(kernel_calls):
+    """The levels kernel decides "starts a stem" at the first position of a chunk of 64 from the last lane of the chunk
+    before, as the score kernels do: the golden rows of Score() that put stems across, up to and from positions 63 | 64 and
+    127 | 128 -- stacked and not, 63 unpaired or a closer, behind gap columns, a pair dropped by a gap on the boundary --
+    in ONE call against the naive reference and the CPU path."""
+    from squarna_amd import Elements
+    cs = [c for c in SC.cases() if c["name"].startswith("boundary_") or c["name"] == "gap_on_the_boundary_pair"]
+    assert len(cs) == 7 and sum(len(c["rows"]) for c in cs) == 59 and sum("-" in c["seq"] for c in cs) == 4
+    recs = [c["seq"] for c in cs]
+    rows = [[SC.partner_row(row["dbn"]) for row in c["rows"]] for c in cs]
+    pad, nstruct = EC.padded(rows, extra=1)
+    res = Elements(records=recs, structures=pad, nstruct=nstruct)
+    _is_device(res)
+    _none_handed_back(kernel_calls, (res,))
+    assert res.status.count_nonzero().item() == 0
+    EC.check_naive(res, recs, rows)
+    EC.equal_results(res, _cpu_elements(records=recs, structures=pad, nstruct=nstruct))
+    assert res.npairs.tolist() == [sum(s[2] for s in row["stems"]) for c in cs for row in c["rows"]]
+
+
 def test_random_rows_on_the_device(kernel_calls):
     from squarna_amd import Elements
     made = [EC.random_row(7 * w + k, w, k=k, gaps=g, sep=s) for w in (5, 30, 150) for k in range(7) for g, s in ((False, False), (True, True))]

@@ -99,6 +99,66 @@ def test_mixed_records_in_one_call(kernel_calls):
     _none_handed_back(kernel_calls, (res,))
 
 
+def test_the_full_sweep_of_the_metric_ratios(kernel_calls):
+    """6,422 rows of six 200-nt records as one padded CUDA tensor: TP = 0 .. K known pairs and FP = 0 .. 96 others for known
+    structures of 0, 1, 3, 16, 48 and 80 pairs.  TP FP FN FS PR RC equal plain Python's round(x, 3) of the ratios, bit for
+    bit -- ties such as 9/16 and the near ties over 80 and 160 among them (tests/test_score_api.py counts those)."""
+    import torch
+    from squarna_amd import Score
+    recs, rows, nstruct, want = SC.sweep()
+    dev = torch.from_numpy(rows).cuda()
+    res = Score(records=recs, structures=dev, nstruct=nstruct)
+    _is_device(res)
+    assert kernel_calls[-1][:2] == (dev.data_ptr(), True) and len(kernel_calls) == 1
+    _none_handed_back(kernel_calls, (res,))
+    host = res.cpu()
+    assert host.row_off.tolist() == np.concatenate([[0], np.cumsum(nstruct)]).tolist()
+    assert host.status.tolist() == [0] * len(want) and kernel_calls[-1][2] == [0] * len(want)
+    assert host.npairs.tolist() == (want[:, 0] + want[:, 1]).tolist()
+    got, counts = host.metrics.numpy(), SC.sweep_counts()
+    wrong = [(counts[q], got[q].tolist(), want[q].tolist()) for q in range(len(want)) if got[q].tobytes() != want[q].tobytes()]
+    assert not wrong, (len(wrong), wrong[:5])
+
+
+def _hands_back(c, stems):
+    """A structure of case c with these golden stems (gap-free coordinates) holds a stem whose pair values sum above 4.0."""
+    value = {"GC": 4.0, "CG": 4.0, "AU": 1.5, "UA": 1.5, "GU": -0.5, "UG": -0.5}
+    short = ''.join(ch for ch in c["seq"].upper().replace("T", "U") if ch not in "-.~")
+    return any(sum(value.get(short[i + t] + short[j - t], 0.0) for t in range(ln)) > 4.0 for i, j, ln in stems)
+
+
+@pytest.mark.parametrize("form", ["strings", "padded"])
+def test_rows_the_kernel_hands_back_are_scored_by_the_host(kernel_calls, monkeypatch, form):
+    """With a power table of 9 entries (a single GC pair is its last) the kernel leaves every row and known structure that
+    holds a stem summing above 4.0 with status 2, and Score() recomputes their scores and metrics on the host and writes
+    them into the device tensors: the result still equals the reference's everywhere."""
+    import torch
+    from squarna_amd import Score
+    from squarna_amd.dbn import DBNToPairs, PairsToStems, UnAlign
+    from squarna_amd.engine import HipEngine
+    full = HipEngine._pow17_table
+    monkeypatch.setattr(HipEngine, "_pow17_table", lambda self, nmax: full(self, nmax)[:9])
+    cs = SC.cases()
+    recs = SC.records_of(cs)
+    if form == "strings":
+        res = Score(records=recs, structures=SC.strings_form(cs))
+    else:
+        padded, nstruct = SC.padded_form(cs, extra=5)
+        res = Score(records=recs, structures=torch.from_numpy(padded).cuda(), nstruct=nstruct)
+    _is_device(res)
+    back = [int(_hands_back(c, row["stems"])) for c in cs for row in c["rows"]]
+    ref_back = []                                                    # (the golden holds no stems of the known structures)
+    for c in cs:
+        known = PairsToStems(sorted(DBNToPairs(UnAlign(c["seq"], c["known"])[1]))) if c["known"] else []
+        ref_back.append(int(_hands_back(c, [(st[0][0][0], st[0][0][1], st[1]) for st in known])))
+    assert 40 < sum(back) < len(back) - 40 and 5 < sum(ref_back) < len(cs) - 5
+    assert len(kernel_calls) == 1
+    assert kernel_calls[0][2] == [2 * b for b in back] and kernel_calls[0][3] == [2 * b for b in ref_back]
+    assert res.recomputed == sum(back) + sum(ref_back)
+    assert res.status.tolist() == [0] * len(back)
+    SC.check_golden(res, cs)                                         # (stems, nstems and npairs of every row are the device's)
+
+
 def test_invalid_rows_on_the_device():
     from squarna_amd import Score
     for name, seq, row in SC.INVALID:
@@ -141,6 +201,28 @@ def test_agrees_with_the_ranking_tail_of_a_fold():
         assert SC.same(np.append(top[best], best + 1), fm[r, 6:13]), recs[r][0]
         checked += 1
     assert checked > 200
+    # Score and the tail share sq_scoring.h, so neither vouches for the other: the counts from the fold's own partner rows
+    # and each record's known pairs with numpy, the ratios with Python's round, the known structure's scores from the host
+    from squarna_amd.score import ScoreRecord
+    partner, cell = fold.partner.cpu().numpy(), fold.cell_off.cpu().numpy()
+    assert not any(ch in "-.~" for rec in recs for ch in rec[1])     # (columns are positions: no pair is dropped)
+    mine = []
+    for r, rec in enumerate(recs):
+        n = len(rec[1])
+        rows, known = partner[cell[r]:cell[r + 1]].reshape(-1, n), SC.partner_row(rec[4])
+        opener = rows > np.arange(n)
+        tp, npairs, nknown = (opener & (rows == known)).sum(1), opener.sum(1), int((known > np.arange(n)).sum())
+        mine.extend(SC.sweep_metrics(nknown, int(t), int(p - t)) for t, p in zip(tp, npairs))
+        own = ScoreRecord(rec[0], rec[1], rec[2], rec[4])
+        assert SC.same(own.score(own.known), fm[r, 13:16]), rec[0]
+    mine = np.array(mine, np.float64)
+    assert mine.shape == host.metrics.shape and mine.tobytes() == host.metrics.numpy().tobytes()
+    assert mine[ro[:-1]].tobytes() == fm[:, :6].tobytes()
+    for r in range(len(recs)):
+        top = mine[ro[r] + 1:ro[r] + 1 + min(int(ro[r + 1] - ro[r]) - 1, 5)]
+        if len(top):
+            best = int(np.argmax(top[:, 3]))
+            assert np.append(top[best], best + 1).tobytes() == fm[r, 6:13].tobytes(), recs[r][0]
 
 
 def test_ten_thousand_rows_of_one_record(kernel_calls):

@@ -85,6 +85,44 @@ def test_structures_none_is_evalonly():
     assert SC.same(res.metrics.numpy(), np.stack([tp, 0 * tp, 0 * tp, 1 + 0 * tp, 1 + 0 * tp, 1 + 0 * tp], axis=1))
 
 
+def test_the_sweep_of_the_metric_ratios_is_not_blind():
+    """A condition on the sweep's INPUTS (tests/score_checks.sweep; run in full by tests/test_hip_score.py): its ratios hold
+    enough distinct (numerator, denominator) on which a subtly wrong round(x, 3) gives another value than the right one --
+    half up on the product, e.g. 9/16 = 0.5625 -> 0.563, and ties to even on the ROUNDED product, e.g. 1/80, whose double
+    lies above 0.0125 while 1000 x rounds to 12.5 exactly -> 0.012."""
+    counts = SC.sweep_counts()
+    assert len(counts) == 6422 and len(set(counts)) == 6422
+    floor_up, product = SC.sweep_telling(SC.round3_floor), SC.sweep_telling(SC.round3_product)
+    assert len(floor_up) >= 40 and len(product) >= 20, (len(floor_up), len(product))
+    assert {(9, 16), (13, 16), (10, 32), (52, 64)} <= floor_up and {(1, 80), (3, 80), (7, 80)} <= product
+    recs, rows, nstruct, want = SC.sweep()
+    assert rows.shape == (6, 2597, 200) and rows.dtype == np.int32 and int(nstruct.sum()) == 6422 and want.shape == (6422, 6)
+    flat = np.concatenate([rows[r, :k] for r, k in enumerate(nstruct)])
+    assert ((flat >= 0).sum(1) == 2 * (want[:, 0] + want[:, 1])).all()                              # TP + FP pairs in every row
+
+
+def test_a_thinned_sweep_of_the_metric_ratios_on_the_host():
+    """Every row of the sweep that holds a ratio on which one of the two wrong roundings differs, and every thirtieth of
+    the others, through the host path: TP FP FN FS PR RC equal plain Python's, bit for bit."""
+    recs, rows, nstruct, want = SC.sweep()
+    telling = SC.sweep_telling(SC.round3_floor) | SC.sweep_telling(SC.round3_product)
+    counts = SC.sweep_counts()
+    holds = np.array([any(r in telling for r in SC.sweep_ratios(*c).values()) for c in counts])
+    other = np.flatnonzero(~holds)
+    pick = np.sort(np.concatenate([np.flatnonzero(holds), other[::len(other) // 200]]))
+    assert int(holds.sum()) > 1000 and 200 <= len(pick) - int(holds.sum()) <= 210
+    first = np.concatenate([[0], np.cumsum(nstruct)])
+    per_record = [pick[(pick >= first[r]) & (pick < first[r + 1])] - first[r] for r in range(len(recs))]
+    thin = np.full((len(recs), max(len(p) for p in per_record), rows.shape[2]), -1, np.int32)
+    for r, p in enumerate(per_record):
+        thin[r, :len(p)] = rows[r, p]
+    res = score(records=recs, structures=thin, nstruct=[len(p) for p in per_record])
+    _is_host(res)
+    assert res.status.count_nonzero().item() == 0 and res.npairs.tolist() == (want[pick, 0] + want[pick, 1]).tolist()
+    got = res.metrics.numpy()
+    assert got.tobytes() == want[pick].tobytes(), [(counts[q], g.tolist(), w.tolist()) for q, g, w in zip(pick, got, want[pick]) if g.tobytes() != w.tobytes()][:5]
+
+
 INVALID = SC.INVALID
 
 
